@@ -6,7 +6,14 @@ full sky, N_side = 512, l_max = 1024, 32 chains per GPU, synthetic data
 (SURVEY.md 8d fiducial), native Philox RNG.  One "step" = one Gibbs
 iteration (constrained realisation + C_l draw) of every chain on every GPU.
 
-  python bench.py [--gpus N --steps K --warmup W --workload NAME]
+  python bench.py [--gpus N --steps K --warmup W --workload NAME] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+--dump-outputs DIR also writes what the last timed step computed as
+DIR/<name>.npy (dump_outputs below).  --full adds the measurements that take
+runs of their own: the CPU baselines (child processes, before the GPU is
+touched) and, for the masked workload, the event-timed alm2map / map2alm
+launches behind its fp64 roofline.
 
   noncentered          configs[2] (default line)
   centered             configs[1] shape (--lmax 512 --nside 256 --nchains 1)
@@ -61,7 +68,14 @@ def parse():
     ap.add_argument("--nside", type=int, default=None, help="512 (masked: 2048; HEAD modes: 256)")
     ap.add_argument("--fields", type=int, default=3, choices=[1, 2, 3])
     ap.add_argument("--seed", type=int, default=20261015)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baselines and the masked "
+                         "workload's separately timed transforms (its fp64 roofline)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step computed (the D_l of every chain, the "
+                         "accept flags, the sky map where the workload keeps one) as DIR/<name>.npy, float64, at "
+                         "most 64 MB in all: an array over 1M elements is written as a fixed, seeded sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--cpu-budget", type=float, default=10.0, help="seconds per CPU baseline leg")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of one hipGraph of the timed steps")
     ap.add_argument("--time-every", type=int, default=None,
@@ -132,6 +146,37 @@ def clock_ramp(args, make_runner, ms):
         g.replay()
         torch.cuda.synchronize()
     return (time.perf_counter() - t0) * 1e3, scratch
+
+
+DUMP_SAMPLE = 1 << 20        # elements kept of a larger output (8 MB in float64)
+DUMP_LIMIT = 64 << 20        # bytes, all files of one dump together
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: write {name: array} (numpy arrays or torch tensors, host or
+    device) as directory/<name>.npy in float64.  An array of more than
+    DUMP_SAMPLE elements is written as the elements at DUMP_SAMPLE flat indices
+    drawn once from numpy's default_rng(0) (sorted; the same indices for the same
+    shape in every run and build), so two builds are compared element for
+    element."""
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        if a is None:
+            continue
+        if not torch.is_tensor(a):
+            a = torch.from_numpy(np.ascontiguousarray(a))
+        flat = a.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).integers(0, flat.numel(), DUMP_SAMPLE))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+            out = flat.to(torch.float64).cpu().numpy()
+        else:
+            out = a.detach().to(torch.float64).cpu().numpy()
+        total += out.nbytes
+        np.save(os.path.join(directory, name + ".npy"), out)
+    assert total <= DUMP_LIMIT, total
 
 
 def sweep_algorithmic_bytes(L, F, nchains, store=True):
@@ -283,7 +328,7 @@ def _finalize_cpu(cpu, cg_iters=None):
 
 def cpu_leg(args):
     """The CPU baseline of this workload (None when it has none)."""
-    if args.no_cpu_baseline:
+    if args.no_cpu_baseline or not args.full:
         return None
     if args.workload == "noncentered":
         return cpu_baseline_child(args)
@@ -443,6 +488,11 @@ def run_harmonic(args, ctx, cpu):
     assert gathered.shape[1] == ctx.global_chains
     if ctx.rank != 0:
         return None
+    if args.dump_outputs:
+        # rank 0's chains after the last timed step: D_l (= the trace's last record),
+        # the last step's accept flags, the sky map when it is stored
+        dump_outputs(args.dump_outputs, {"dl": runner.dl, "accept": runner.accept if p.nacc else None,
+                                         "skymap": runner.s})
     total = args.steps * ctx.global_chains
     sweep_avg_ms = sweep_ms / max(sweep_n, 1)
     alg_bytes = sweep_algorithmic_bytes(p.L, p.F, p.nchains, store=args.skymap == "store")
@@ -515,6 +565,8 @@ def run_surface(args, ctx):
         return None
     hist = out[0]
     assert np.asarray(hist["EE"]).shape[0] == args.steps + 1
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {f"dl_{sp}": np.asarray(h)[-1] for sp, h in hist.items()})
     total = args.steps * ctx.global_chains
     return {
         "metric": METRIC % (N, L), "value": round(total / elapsed, 3), "unit": "chain-iterations/s",
@@ -587,6 +639,7 @@ def masked_c5_setup(args, ctx):
         out = plan.cls_draw(st, None, seed=args.seed, iteration=it[0])
         dl_t.copy_(out[:, :, :L + 1])          # unbinned bins: bin b = l
 
+    step.outputs = lambda: {"dl": dl_t, "skymap": s}
     return step
 
 
@@ -612,26 +665,30 @@ def run_masked(args, ctx, cpu=None):
         step()
     torch.cuda.synchronize()
     elapsed = ctx.max(time.perf_counter() - t0)
-    # the transforms the step runs, timed with events on the launch stream
-    sht = HealpixSHT(N, L)
-    a = torch.zeros((3, NR), dtype=torch.float64, device="cuda")
-    mp = torch.zeros((3, Npix), dtype=torch.float64, device="cuda")
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-    reps = 3
-    ev[0].record()
-    for _ in range(reps):
-        sht.alm2map(a, ncomp=3, out=mp)
-    ev[1].record()
-    for _ in range(reps):
-        sht.map2alm(mp, iter=0, ncomp=3, out=a)
-    ev[2].record()
-    torch.cuda.synchronize()
-    t_syn = ev[0].elapsed_time(ev[1]) / reps
-    t_ana = ev[1].elapsed_time(ev[2]) / reps
+    if args.dump_outputs and ctx.rank == 0:
+        dump_outputs(args.dump_outputs, step.outputs())
+    fl = sht_flops(N, L, 20)
+    t_syn = t_ana = achieved = None
+    if args.full:
+        # the transforms the step runs, timed with events on the launch stream
+        sht = HealpixSHT(N, L)
+        a = torch.zeros((3, NR), dtype=torch.float64, device="cuda")
+        mp = torch.zeros((3, Npix), dtype=torch.float64, device="cuda")
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        reps = 3
+        ev[0].record()
+        for _ in range(reps):
+            sht.alm2map(a, ncomp=3, out=mp)
+        ev[1].record()
+        for _ in range(reps):
+            sht.map2alm(mp, iter=0, ncomp=3, out=a)
+        ev[2].record()
+        torch.cuda.synchronize()
+        t_syn = ev[0].elapsed_time(ev[1]) / reps
+        t_ana = ev[1].elapsed_time(ev[2]) / reps
+        achieved = 2 * fl / ((t_syn + t_ana) * 1e-3) / 1e12
     if ctx.rank != 0:
         return None
-    fl = sht_flops(N, L, 20)
-    achieved = 2 * fl / ((t_syn + t_ana) * 1e-3) / 1e12
     # HBM bytes of one whole step (every kernel between two markers,
     # tools/step_traffic.py + tools/summarize_step_traffic.py): profiles/pmc_traffic.json
     tp = load_profile(args.profile_json, f"step_masked_N{N}_L{L}_B{B}_{args.mask}")
@@ -646,15 +703,19 @@ def run_masked(args, ctx, cpu=None):
         "config": {"workload": "centered TEB masked aux-variable CR (n_gibbs=1)", "nside": N, "lmax": L,
                    "nfields": 3, "chains_per_gpu": B, "global_chains": B * ctx.world,
                    "rng": "native philox4x32-10", "parallelism": f"chains sharded over {ctx.world} GPU(s)"},
-        "roofline": {"bound": "fp64", "kernel": "gs_sht alm2map + map2alm (TEB)", "achieved": round(achieved, 2),
-                     "peak": FP64_VALU_PEAK_TFS, "unit": "TFLOP/s", "frac": round(achieved / FP64_VALU_PEAK_TFS, 4),
+        # achieved / frac / avg_launch_ms: the transforms' own timed launches, --full only
+        "roofline": {"bound": "fp64", "kernel": "gs_sht alm2map + map2alm (TEB)",
+                     "achieved": round(achieved, 2) if args.full else None,
+                     "peak": FP64_VALU_PEAK_TFS, "unit": "TFLOP/s",
+                     "frac": round(achieved / FP64_VALU_PEAK_TFS, 4) if args.full else None,
                      "traffic": tp.get("hbm_bytes_per_step"),
                      "traffic_unit": "HBM bytes per step (every kernel of one step, PMC)",
                      "traffic_over_algorithmic": tp.get("traffic_over_algorithmic"),
                      "algorithmic_bytes_per_step": tp.get("algorithmic_bytes_per_step"),
                      "traffic_source": tp.get("source"),
                      "algorithmic_flops_per_launch": fl,
-                     "avg_launch_ms": {"alm2map": round(t_syn, 3), "map2alm": round(t_ana, 3)}},
+                     "avg_launch_ms": {"alm2map": round(t_syn, 3), "map2alm": round(t_ana, 3)} if args.full
+                     else None},
         "cpu_baseline": _finalize_cpu(cpu),
         "notes": "healpy is absent: the CPU leg's transforms are oracle/sht_cpu.cpp (C++/OpenMP); see DESIGN.md",
     }
@@ -750,11 +811,15 @@ def run_masked_head(args, ctx, cpu=None):
     torch.cuda.synchronize()
     n_solves0 = len(pcg.pcg_iterations) if pcg is not None else 0
     t0 = time.perf_counter()
-    go()
+    out = go()
     torch.cuda.synchronize()
     elapsed = ctx.max(time.perf_counter() - t0)
     if ctx.rank != 0:
         return None
+    if args.dump_outputs:
+        # run()'s D_l histories, their last record, and the runner's sky map
+        dump_outputs(args.dump_outputs, {**{f"dl_{sp}": np.asarray(h)[-1] for sp, h in out[0].items()},
+                                         "skymap": runner.s})
     pcg_info = None
     if pcg is not None:
         its = pcg.pcg_iterations[n_solves0:]

@@ -4,13 +4,13 @@ main_polarization.py (lines 1-2, 7-9) resolve to this package, its constructor
 calls (main_polarization.py:109-126) bind to the classes' signatures, and every
 ``config.<name>`` / ``<sampler>.constrained_sampler.<name>`` it reads exists.
 
-The caller is read from /root/reference when it is present (parsed with ast,
-as text; nothing of it is executed or copied); otherwise the test restates
-only the keyword names of those calls.  CPU only: binding checks signatures,
-nothing is constructed on a device."""
-import ast
+The caller's side is stored as names only (tests/golden/main_polarization_names.json:
+the names it imports, the positional count and keyword names of its constructor
+calls, the config attributes it reads); nothing of the caller is executed or
+copied.  CPU only: binding checks signatures, nothing is constructed on a device."""
 import importlib
 import inspect
+import json
 import os
 import sys
 
@@ -18,18 +18,13 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DROPIN = os.path.join(ROOT, "dropin")
-CALLER = "/root/reference/main_polarization.py"
+NAMES = os.path.join(ROOT, "tests", "golden", "main_polarization_names.json")
 REF_MODULES = ("utils", "config", "NonCenteredGibbs", "ASIS", "CenteredGibbs")
 
-# keyword names of main_polarization.py:109-126 (fallback when the caller is absent)
-_FALLBACK_CALLS = {
-    "CenteredGibbs": [8, ["mask_path", "polarization", "bins", "n_iter", "rj_step", "gibbs_cr", "overrelaxation",
-                          "ula"]],
-    "NonCenteredGibbs": [7, ["mask_path", "polarization", "bins", "n_iter", "proposal_variances",
-                             "metropolis_blocks", "all_sph"]],
-    "ASIS": [7, ["mask_path", "polarization", "bins", "n_iter", "proposal_variances", "metropolis_blocks",
-                 "rj_step", "all_sph", "gibbs_cr", "n_gibbs", "overrelaxation"]],
-}
+
+def _caller_names():
+    with open(NAMES) as f:
+        return json.load(f)
 
 
 @pytest.fixture
@@ -45,28 +40,6 @@ def dropin_modules():
         sys.modules.update(saved)
 
 
-def _caller_tree():
-    if not os.path.exists(CALLER):
-        return None
-    import warnings
-    with open(CALLER) as f, warnings.catch_warnings():
-        warnings.simplefilter("ignore", DeprecationWarning)     # the caller's docstring escapes
-        return ast.parse(f.read())
-
-
-def _constructor_calls(tree):
-    """(class name, positional count, keyword names) of every call of the
-    three sampler classes in the caller."""
-    if tree is None:
-        return [(k, n, kw) for k, (n, kw) in _FALLBACK_CALLS.items()]
-    out = []
-    for node in ast.walk(tree):
-        if isinstance(node, ast.Call) and isinstance(node.func, ast.Name) and \
-                node.func.id in ("CenteredGibbs", "NonCenteredGibbs", "ASIS"):
-            out.append((node.func.id, len(node.args), [k.arg for k in node.keywords]))
-    return out
-
-
 def test_reference_imports_resolve_to_this_package(dropin_modules):
     import gibbssampler_amd.config as gcfg
     import gibbssampler_amd.gibbs as gg
@@ -76,21 +49,18 @@ def test_reference_imports_resolve_to_this_package(dropin_modules):
     assert m["CenteredGibbs"].CenteredGibbs is gg.CenteredGibbs
     assert m["NonCenteredGibbs"].NonCenteredGibbs is gg.NonCenteredGibbs
     assert m["ASIS"].ASIS is gg.ASIS
-    tree = _caller_tree()
-    if tree is not None:
-        for node in ast.walk(tree):
-            if isinstance(node, ast.ImportFrom) and node.module in REF_MODULES:
-                for a in node.names:
-                    assert hasattr(m[node.module], a.name), (node.module, a.name)
-            elif isinstance(node, ast.Import):
-                for a in node.names:
-                    if a.name in REF_MODULES:
-                        assert a.name in m
+    names = _caller_names()
+    for module, attrs in names["imports_from"].items():
+        assert module in REF_MODULES
+        for a in attrs:
+            assert hasattr(m[module], a), (module, a)
+    for module in names["imports"]:
+        assert module in m
 
 
 def test_constructor_calls_bind(dropin_modules):
     m = dropin_modules
-    calls = _constructor_calls(_caller_tree())
+    calls = _caller_names()["constructor_calls"]
     assert {c[0] for c in calls} == {"CenteredGibbs", "NonCenteredGibbs", "ASIS"}
     for name, npos, kws in calls:
         cls = getattr(m[name], name)
@@ -100,14 +70,8 @@ def test_constructor_calls_bind(dropin_modules):
 
 def test_config_and_attribute_reads_exist(dropin_modules):
     cfg = dropin_modules["config"]
-    tree = _caller_tree()
-    names = {"NSIDE", "L_MAX_SCALARS", "Npix", "beam_fwhm", "mask_path", "bins", "blocks",
-             "proposal_variances_nc_polarized", "noise_covar_temp", "noise_covar_pol", "bl_gauss",
-             "preliminary_run", "starting_point", "scratch_path", "slurm_task_id", "COSMO_PARAMS_MEAN_PRIOR",
-             "fwhm_radians", "var_noise_temp", "var_noise_pol"}
-    if tree is not None:
-        names |= {n.attr for n in ast.walk(tree) if isinstance(n, ast.Attribute) and isinstance(n.value, ast.Name)
-                  and n.value.id == "config"}
+    names = set(_caller_names()["config_attributes"])
+    assert len(names) >= 19
     missing = sorted(n for n in names if not hasattr(cfg, n))
     assert not missing, missing
     assert cfg.NSIDE == 256 and cfg.L_MAX_SCALARS == 512 and len(cfg.bins["BB"]) == 413

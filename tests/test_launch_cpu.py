@@ -86,3 +86,49 @@ def test_bench_parse_defaults(monkeypatch):
     a = bench.parse()
     assert (a.nchains, a.lmax, a.nside, a.steps) == (1, 512, 256, 5)
     assert a.opt == ["GS_SHT_MERGE_RINGS=0"]
+
+
+def test_bench_plain_run_has_no_cpu_leg(monkeypatch):
+    """A plain run measures the headline figure only: the CPU baselines (child
+    processes) start with --full, and --no-cpu-baseline still turns them off."""
+    import bench
+    started = []
+    monkeypatch.setattr(bench, "cpu_baseline_child", lambda a: started.append(a.workload) or {"value": 1.0})
+    monkeypatch.setattr(bench, "cpu_baseline_masked_child", lambda a: started.append(a.workload) or {"value": 1.0})
+    for argv, want in ((["--gpus", "1", "--steps", "20", "--warmup", "5"], []),
+                       (["--workload", "masked"], []),
+                       (["--full"], ["noncentered"]),
+                       (["--full", "--workload", "masked"], ["masked"]),
+                       (["--full", "--workload", "masked_asis"], ["masked_asis"]),
+                       (["--full", "--no-cpu-baseline"], [])):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+        a = bench.parse()
+        assert a.full == ("--full" in argv) and a.dump_outputs is None
+        del started[:]
+        assert (bench.cpu_leg(a) is not None) == bool(want)
+        assert started == want
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs: float64 .npy files; an array over DUMP_SAMPLE elements is
+    written as the same seeded sample of its flat elements in every call, tensors
+    and arrays alike; None entries are left out."""
+    import numpy as np
+    import torch
+    import bench
+    small = np.arange(24, dtype=np.float32).reshape(2, 3, 4)
+    big = torch.arange(bench.DUMP_SAMPLE + 12344,dtype=torch.float64).reshape(-1, 5) * 0.5
+    flags = torch.tensor([[1, 0], [0, 1]], dtype=torch.int32)
+    d1, d2 = str(tmp_path / "a"), str(tmp_path / "b" / "c")
+    bench.dump_outputs(d1, {"dl": small, "skymap": big, "accept": flags, "absent": None})
+    bench.dump_outputs(d2, {"skymap": big.numpy().copy()})
+    assert sorted(os.listdir(d1)) == ["accept.npy", "dl.npy", "skymap.npy"]
+    dl, acc, sk = (np.load(os.path.join(d1, n + ".npy")) for n in ("dl", "accept", "skymap"))
+    assert dl.dtype == np.float64 and dl.shape == small.shape and np.array_equal(dl, small)
+    assert acc.dtype == np.float64 and np.array_equal(acc, flags.numpy())
+    assert sk.dtype == np.float64 and sk.shape == (bench.DUMP_SAMPLE,)
+    idx = 2.0 * sk                                   # the element at flat index i is i / 2
+    assert np.all(np.diff(idx) >= 0) and idx[0] >= 0 and idx[-1] < big.numel()
+    assert len(np.unique(idx)) > 0.6 * bench.DUMP_SAMPLE
+    assert np.array_equal(sk, np.load(os.path.join(d2, "skymap.npy")))
+    assert sum(os.path.getsize(os.path.join(d1, f)) for f in os.listdir(d1)) <= bench.DUMP_LIMIT

@@ -20,6 +20,7 @@ TAG=${1:-r03}
 PART=${2:-all}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/prof_$TAG
+RES=$(dirname "$OUT")   # the bench lines go next to the profiles
 if [ "$PART" = a ] || [ "$PART" = p ] || [ "$PART" = all ]; then
 rm -rf "$OUT"
 mkdir -p "$OUT"
@@ -44,7 +45,8 @@ fi
 # h: the harmonic bench lines alone (after summarize_profile.py has folded part p's passes into
 # profiles/pmc_traffic.json, so the lines' roofline reads this build's counters)
 if [ "$PART" = a ] || [ "$PART" = h ] || [ "$PART" = all ]; then
-timeout -k 10 400 python3 bench.py > gpurun_out/bench_${TAG}_default.json 2> gpurun_out/bench_${TAG}_default.err
+# --full: the line with its cpu_baseline
+timeout -k 10 400 python3 bench.py --full > "$RES/bench_${TAG}_default.json" 2> "$RES/bench_${TAG}_default.err"
 timeout -k 10 400 python3 bench.py --no-cpu-baseline --skymap store > gpurun_out/bench_${TAG}_default_store.json \
     2> gpurun_out/bench_${TAG}_default_store.err
 timeout -k 10 300 python3 bench.py --workload centered --nside 256 --lmax 512 --nchains 1 --time-every 100 \
@@ -86,8 +88,8 @@ exit 0
 fi
 if [ "$PART" = d ]; then
 for m in masked_asis masked_centered_ula masked_centered_pcg masked_noncentered; do
-    timeout -k 10 300 python3 bench.py --workload $m --nchains 16 > gpurun_out/bench_${TAG}_${m}_b16.json \
-        2> gpurun_out/bench_${TAG}_${m}_b16.err
+    timeout -k 10 300 python3 bench.py --full --workload $m --nchains 16 > "$RES/bench_${TAG}_${m}_b16.json" \
+        2> "$RES/bench_${TAG}_${m}_b16.err"
 done
 rm -rf "${OUT}_pcg_b16"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "${OUT}_pcg_b16" -o run --output-format csv -- \
@@ -112,10 +114,10 @@ exit 0
 fi
 if [ "$PART" = b ] || [ "$PART" = all ]; then
 rm -rf "${OUT}_masked" "${OUT}_sht" "${OUT}_masked_asis" "${OUT}_c2"
-timeout -k 10 600 python3 bench.py --workload masked > gpurun_out/bench_${TAG}_masked_C5.json \
-    2> gpurun_out/bench_${TAG}_masked_C5.err
+timeout -k 10 600 python3 bench.py --full --workload masked > "$RES/bench_${TAG}_masked_C5.json" \
+    2> "$RES/bench_${TAG}_masked_C5.err"
 for m in masked_asis masked_centered_ula masked_centered_pcg masked_noncentered; do
-    timeout -k 10 300 python3 bench.py --workload $m > gpurun_out/bench_${TAG}_$m.json 2> gpurun_out/bench_${TAG}_$m.err
+    timeout -k 10 300 python3 bench.py --full --workload $m > "$RES/bench_${TAG}_$m.json" 2> "$RES/bench_${TAG}_$m.err"
 done
 echo "bench lines done"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "${OUT}_c2" -o run --output-format csv -- \
