@@ -95,7 +95,20 @@ struct gs_plan {
     int sweep_tw = 4, nchunkg = 0;   // tiles per sweep workgroup, chunks per tile
     int ntask = 0;                   // valid (tile, chunk) waves per chain
     // workspace
-    double* partials = nullptr;      // [nchains][ntile][nchunkg][nstat][64]
+    double* partials = nullptr;      // [nchains][ntile][nchunkg][nstat or raw sums][64]
+    // raw-moment statistics of native-draw NC steps (GS_NC_RAW=0|1, default 1):
+    // the sweep accumulates sum z z^T and sum d z^T, which need no operator, and
+    // the statistics finish applies the operator of the chain's D_l to them and
+    // to the data moments sum d d^T of the tensor gs_data_moments last saw
+    bool raw_on = true;
+    double* dmom = nullptr;          // [ND][L+1] data moments
+    const double* dmom_src = nullptr;    // the data tensor they belong to
+    bool raw_pending = false;        // the partials hold raw sums (of a sweep at raw_dl)
+    const double* raw_dl = nullptr;
+    // many-chain native NC steps: the prologue's parameter table is launched by
+    // gs_nc_sweep only when its sweep needs it (replayed normals, stored map)
+    bool par_pending = false;
+    const double* par_dl = nullptr;
     double* params = nullptr;        // [nchains][L+1][NP]
     double* stats = nullptr;         // [nchains][nstat][L+1]
     double* prop = nullptr;          // [nchains][nspec][maxbins]
@@ -250,6 +263,13 @@ __global__ __launch_bounds__(256) void k_block_params(int L, int nchains, int ma
 template <int F>
 struct SweepAcc {
     static constexpr int NS = F == 1 ? GS_NSTAT_1 : (F == 2 ? GS_NSTAT_2 : GS_NSTAT_3);
+    // raw-moment form (native-draw NC steps): the sums over m of z z^T and d z^T,
+    // which do not depend on the chain's D_l.  F = 3: z0^2, z0 z1, z1^2, z2^2,
+    // d0 z0, d1 z0, d0 z1, d1 z1, d2 z2; otherwise z_f^2, d_f z_f.
+    static constexpr int NRAW = F == 3 ? 9 : 2 * F;
+    // data moments sum_m d d^T per l.  F = 3: d0^2, d0 d1, d1^2, d2^2; otherwise d_f^2
+    static constexpr int ND = F == 3 ? 4 : F;
+    static constexpr int n(bool raw) { return raw ? NRAW : NS; }
     double v[NS];
 };
 
@@ -275,12 +295,16 @@ __device__ __forceinline__ void load_d2_off(const char* const (&db)[F], uint32_t
     }
 }
 
-// ZM: 0 native RNG draw, 1 replay (z from memory), 2 statistics of a given s
-template <int F, int ZM, bool STORE, int NV>
+// ZM: 0 native RNG draw, 1 replay (z from memory), 2 statistics of a given s.
+// RAW (ZM == 0 only): the accumulators are the raw moments of (d, z) instead of
+// the statistics of s = P d + Q z; the statistics finish applies the operator
+// (k_stats_finish_raw).  s itself is formed only when it is stored.
+template <int F, int ZM, bool STORE, int NV, bool RAW = false>
 __device__ __forceinline__ void sweep_entry(const double (&dv)[F][2], const double* __restrict__ zc,
                                             double* __restrict__ sc, long long NR, long long r, uint32_t i,
                                             uint32_t tag, uint32_t iter, Key key, const double (&pm)[NP],
-                                            double (&acc)[SweepAcc<F>::NS], const double* __restrict__ tab) {
+                                            double (&acc)[SweepAcc<F>::n(RAW)], const double* __restrict__ tab) {
+    static_assert(!RAW || ZM == 0, "raw moments: native draws only");
     double zv[F][2], sv[F][NV];
     if constexpr (ZM == 2) {
 #pragma unroll
@@ -297,6 +321,7 @@ __device__ __forceinline__ void sweep_entry(const double (&dv)[F][2], const doub
             box_muller_tab(philox<true>(i, (uint32_t)f, tag, iter, key), tab, zv[f][0], zv[f][1]);
         }
     }
+    if constexpr (!RAW || STORE) {
 #pragma unroll
     for (int c = 0; c < NV; ++c) {
         if constexpr (F == 3) {
@@ -309,6 +334,7 @@ __device__ __forceinline__ void sweep_entry(const double (&dv)[F][2], const doub
         }
     }
     }
+    }
     if constexpr (STORE) {
         // streaming output: non-temporal stores keep the data tiles in L2
 #pragma unroll
@@ -317,6 +343,29 @@ __device__ __forceinline__ void sweep_entry(const double (&dv)[F][2], const doub
             for (int c = 0; c < NV; ++c) {
                 __builtin_nontemporal_store(sv[f][c], &sc[f * NR + r + c]);
             }
+    }
+    if constexpr (RAW) {
+#pragma unroll
+        for (int c = 0; c < NV; ++c) {
+            if constexpr (F == 3) {
+                acc[0] += zv[0][c] * zv[0][c];
+                acc[1] += zv[0][c] * zv[1][c];
+                acc[2] += zv[1][c] * zv[1][c];
+                acc[3] += zv[2][c] * zv[2][c];
+                acc[4] += dv[0][c] * zv[0][c];
+                acc[5] += dv[1][c] * zv[0][c];
+                acc[6] += dv[0][c] * zv[1][c];
+                acc[7] += dv[1][c] * zv[1][c];
+                acc[8] += dv[2][c] * zv[2][c];
+            } else {
+#pragma unroll
+                for (int f = 0; f < F; ++f) {
+                    acc[f] += zv[f][c] * zv[f][c];
+                    acc[F + f] += dv[f][c] * zv[f][c];
+                }
+            }
+        }
+        return;
     }
 #pragma unroll
     for (int c = 0; c < NV; ++c) {
@@ -414,14 +463,15 @@ __device__ __forceinline__ void sweep_partials_store(const double (&acc)[NS], in
 // Box-Muller tables, the operator's D_l -- is issued before any of them is
 // used (one memory round trip instead of one per row plus two for the
 // prologue).  Same arithmetic in the same order as the throughput form below.
-template <int F, bool STORE, int PRE>
+template <int F, bool STORE, int PRE, bool RAW = false>
 __device__ __forceinline__ void cr_sweep_latency(int L, int nchains, int ntile, int nchunkg, int tm, int tw,
                                                  const int2* __restrict__ tasks, const double* __restrict__ d,
                                                  double* __restrict__ s,
                                                  double* __restrict__ partials, uint32_t seed_lo, uint32_t seed_hi,
                                                  uint32_t iter, uint32_t substep, int chain0, const SweepOp& op,
                                                  double* tab, double* red, int bid = -1, int nwg = 0) {
-    constexpr int NS = SweepAcc<F>::NS;
+    constexpr int NS = SweepAcc<F>::n(RAW);
+    constexpr bool OP = !RAW || STORE;          // the operator is needed (to form s)
     if (bid < 0) { bid = blockIdx.x; nwg = gridDim.x; }
     const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
     const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
@@ -450,8 +500,10 @@ __device__ __forceinline__ void cr_sweep_latency(int L, int nchains, int ntile, 
     constexpr int NSP = F == 1 ? 1 : (F == 2 ? 2 : 4);
     const int lc = max(ell, 0);
     int bidx[NSP];
+    if constexpr (OP) {
 #pragma unroll
-    for (int q = 0; q < NSP; ++q) bidx[q] = op.ell2bin[q * (L + 1) + lc];
+        for (int q = 0; q < NSP; ++q) bidx[q] = op.ell2bin[q * (L + 1) + lc];
+    }
     double dq[PRE][F][2];
     {
         const int mlast = max(m1 - 1, m0);
@@ -471,9 +523,11 @@ __device__ __forceinline__ void cr_sweep_latency(int L, int nchains, int ntile, 
         const int j = threadIdx.x + 256 * k;
         tv[k] = j < BM_LOG_DOUBLES ? BM_LOG_TAB[j] : BM_TRIG_TAB[min(j - BM_LOG_DOUBLES, 511)];
     }
-    const double bq = op.bl[lc];
     // 3. this l's D_l (the latency form always computes the operator in-kernel,
     //    op.mode >= 0; an unbinned l reads bin 0 and drops it)
+    double pm[NP];
+    if constexpr (OP) {
+    const double bq = op.bl[lc];
     double dlq[NSP];
     {
         const double* dlc = op.dl + (long long)chain * NSP * op.maxbins;
@@ -483,11 +537,14 @@ __device__ __forceinline__ void cr_sweep_latency(int L, int nchains, int ntile, 
         for (int q = 0; q < NSP; ++q) dlq[q] = bidx[q] < 0 ? 0.0 : dlq[q];
     }
     // 4. the operator
-    double pm[NP];
     if (op.mode == GS_MODE_CENTERED)
         block_params_from<F, GS_MODE_CENTERED>(lc, bq, dlq, op.k0, op.k1, op.k2, pm);
     else
         block_params_from<F, GS_MODE_NONCENTERED>(lc, bq, dlq, op.k0, op.k1, op.k2, pm);
+    } else {
+#pragma unroll
+        for (int q = 0; q < NP; ++q) pm[q] = 0.0;   // never read: the raw moments need no operator
+    }
 #pragma unroll
     for (int k = 0; k < (BM_TAB_DOUBLES + 255) / 256; ++k) {
         const int j = threadIdx.x + 256 * k;
@@ -505,11 +562,12 @@ __device__ __forceinline__ void cr_sweep_latency(int L, int nchains, int ntile, 
         const int m = m0 + k;
         if (active && m < m1 && lane_ok && ell >= m) {
             if (m == 0) {
-                sweep_entry<F, 0, STORE, 1>(dq[k], nullptr, sc, NR, ell, (uint32_t)ell, tag, iter, key, pm, acc, tab);
+                sweep_entry<F, 0, STORE, 1, RAW>(dq[k], nullptr, sc, NR, ell, (uint32_t)ell, tag, iter, key, pm, acc,
+                                                 tab);
             } else {
                 const long long i = (long long)m * (2 * L + 1 - m) / 2 + ell;
-                sweep_entry<F, 0, STORE, 2>(dq[k], nullptr, sc, NR, 2 * i - (L + 1), (uint32_t)i, tag, iter, key, pm,
-                                            acc, tab);
+                sweep_entry<F, 0, STORE, 2, RAW>(dq[k], nullptr, sc, NR, 2 * i - (L + 1), (uint32_t)i, tag, iter, key,
+                                                 pm, acc, tab);
             }
         }
     }
@@ -567,7 +625,7 @@ __device__ unsigned long long g_sw_tl[4 * SW_TL_MAX];
 #endif
 
 // one (tile group, row chunk) task of one chain: logical workgroup wg
-template <int F, int ZM, bool STORE>
+template <int F, int ZM, bool STORE, bool RAW = false>
 __device__ __forceinline__ void cr_sweep_task(int wg, int L, int nchains, int ntile, int nchunkg, int tm, int tw,
                                               const int2* __restrict__ tasks, const double* __restrict__ d,
                                               const double* __restrict__ params, const double* __restrict__ z,
@@ -575,7 +633,7 @@ __device__ __forceinline__ void cr_sweep_task(int wg, int L, int nchains, int nt
                                               uint32_t seed_lo, uint32_t seed_hi, uint32_t iter, uint32_t substep,
                                               int chain0, const SweepOp& op, const double* __restrict__ tab,
                                               double* red) {
-    constexpr int NS = SweepAcc<F>::NS;
+    constexpr int NS = SweepAcc<F>::n(RAW);
     const int pair = wg / nchains;
     const int chain = wg % nchains;
     const int lane = threadIdx.x & 63;
@@ -597,7 +655,8 @@ __device__ __forceinline__ void cr_sweep_task(int wg, int L, int nchains, int nt
     const uint32_t tag = TAG_CR | (substep << 8);
 
     double pm[NP];
-    sweep_operator<F>(ZM != 2 && lane_ok && active, chain, ell, L, params, op, pm);
+    // (raw moments without the map: no operator is read or computed)
+    sweep_operator<F>(ZM != 2 && (!RAW || STORE) && lane_ok && active, chain, ell, L, params, op, pm);
     double acc[NS];
 #pragma unroll
     for (int q = 0; q < NS; ++q) acc[q] = 0.0;
@@ -610,7 +669,7 @@ __device__ __forceinline__ void cr_sweep_task(int wg, int L, int nchains, int nt
     if (active && m == 0) {
         if (lane_ok) {
             load_d<F, 1>(d, NR, ell, dv);
-            sweep_entry<F, ZM, STORE, 1>(dv, zc, sc, NR, ell, (uint32_t)ell, tag, iter, key, pm, acc, tab);
+            sweep_entry<F, ZM, STORE, 1, RAW>(dv, zc, sc, NR, ell, (uint32_t)ell, tag, iter, key, pm, acc, tab);
         }
         m = 1;
     }
@@ -629,14 +688,14 @@ __device__ __forceinline__ void cr_sweep_task(int wg, int L, int nchains, int nt
             for (; m < m1; ++m) {
                 const uint32_t r = 2u * i32 - (uint32_t)(L + 1);
                 load_d2_off<F>(db, r * 8u, dv);
-                sweep_entry<F, ZM, STORE, 2>(dv, zc, sc, NR, (long long)r, i32, tag, iter, key, pm, acc, tab);
+                sweep_entry<F, ZM, STORE, 2, RAW>(dv, zc, sc, NR, (long long)r, i32, tag, iter, key, pm, acc, tab);
                 GS_ASSERT((long long)r + 1 < NR && (long long)r > L);
                 i32 += (uint32_t)(L - m);
             }
         } else {
         for (; m < m1; ++m) {
             load_d<F, 2>(d, NR, 2 * i - (L + 1), dv);
-            sweep_entry<F, ZM, STORE, 2>(dv, zc, sc, NR, 2 * i - (L + 1), (uint32_t)i, tag, iter, key, pm, acc, tab);
+            sweep_entry<F, ZM, STORE, 2, RAW>(dv, zc, sc, NR, 2 * i - (L + 1), (uint32_t)i, tag, iter, key, pm, acc, tab);
             GS_ASSERT(2 * i - (L + 1) + 1 < NR && 2 * i - (L + 1) > L);
             i += L - m;
         }
@@ -652,7 +711,7 @@ __device__ __forceinline__ void cr_sweep_task(int wg, int L, int nchains, int nt
             if (lane_ok && ell >= m) {
                 const uint32_t r = 2u * i32 - (uint32_t)(L + 1);
                 load_d2_off<F>(db, r * 8u, dv);
-                sweep_entry<F, ZM, STORE, 2>(dv, zc, sc, NR, (long long)r, i32, tag, iter, key, pm, acc, tab);
+                sweep_entry<F, ZM, STORE, 2, RAW>(dv, zc, sc, NR, (long long)r, i32, tag, iter, key, pm, acc, tab);
             }
             i32 += (uint32_t)(L - m);
         }
@@ -660,7 +719,7 @@ __device__ __forceinline__ void cr_sweep_task(int wg, int L, int nchains, int nt
         for (; m < m1; ++m) {
             if (lane_ok && ell >= m) {
                 load_d<F, 2>(d, NR, 2 * i - (L + 1), dv);
-                sweep_entry<F, ZM, STORE, 2>(dv, zc, sc, NR, 2 * i - (L + 1), (uint32_t)i, tag, iter, key, pm,
+                sweep_entry<F, ZM, STORE, 2, RAW>(dv, zc, sc, NR, 2 * i - (L + 1), (uint32_t)i, tag, iter, key, pm,
                                                  acc, tab);
             }
             i += L - m;
@@ -679,7 +738,7 @@ __device__ __forceinline__ void cr_sweep_task(int wg, int L, int nchains, int nt
 #ifndef GS_SWEEP_MINW
 #define GS_SWEEP_MINW 1
 #endif
-template <int F, int ZM, bool STORE, int PRE = 0>
+template <int F, int ZM, bool STORE, int PRE = 0, bool RAW = false>
 __global__ __launch_bounds__(256, GS_SWEEP_MINW) void k_cr_sweep(int L, int nchains, int ntile, int nchunkg, int tm, int tw,
                                                   const int2* __restrict__ tasks, const double* __restrict__ d,
                                                   const double* __restrict__ params, const double* __restrict__ z,
@@ -693,7 +752,7 @@ __global__ __launch_bounds__(256, GS_SWEEP_MINW) void k_cr_sweep(int L, int ncha
         }
     }
     const uint32_t iter = itarg.get();
-    constexpr int NS = SweepAcc<F>::NS;
+    constexpr int NS = SweepAcc<F>::n(RAW);
     __shared__ __attribute__((aligned(16))) double tab[ZM == 0 ? BM_TAB_DOUBLES : 2];
     __shared__ double red[3 * NS * WAVE];           // chunk-wave sums of tw < 4 shapes
     if constexpr (PRE > 0) {
@@ -707,7 +766,7 @@ __global__ __launch_bounds__(256, GS_SWEEP_MINW) void k_cr_sweep(int L, int ncha
                                  chain0);
             return;
         }
-        cr_sweep_latency<F, STORE, PRE>(L, nchains, ntile, nchunkg, tm, tw, tasks, d, s, partials, seed_lo,
+        cr_sweep_latency<F, STORE, PRE, RAW>(L, nchains, ntile, nchunkg, tm, tw, tasks, d, s, partials, seed_lo,
                                         seed_hi, iter, substep, chain0, op, tab, red, (int)blockIdx.x, nsw);
         return;
     }
@@ -725,7 +784,7 @@ __global__ __launch_bounds__(256, GS_SWEEP_MINW) void k_cr_sweep(int L, int ncha
 #if defined(GS_SWEEP_WGTIME)
     const unsigned long long tl0 = wall_clock64();
 #endif
-    cr_sweep_task<F, ZM, STORE>(base + (bid >> 3), L, nchains, ntile, nchunkg, tm, tw, tasks, d, params, z, s,
+    cr_sweep_task<F, ZM, STORE, RAW>(base + (bid >> 3), L, nchains, ntile, nchunkg, tm, tw, tasks, d, params, z, s,
                                 partials, seed_lo, seed_hi, iter, substep, chain0, op, tab, red);
 #if defined(GS_SWEEP_WGTIME)
     __syncthreads();
@@ -1193,6 +1252,168 @@ __global__ __launch_bounds__(256) void k_stats_finish_pro(int L, int nchains, in
         if (ell >= 0)
             stats[((long long)chain * nstat + q) * Lp1 + ell] = ((red[0][lane] + red[1][lane]) + red[2][lane]) +
                                                                  red[3][lane];
+    }
+}
+
+// sum_m d d^T per l of one data tensor [F][(L+1)^2] (SweepAcc<F>::ND rows of L + 1):
+// one thread per l adds its rows m = 0 .. l in order (m = 0 once, m > 0 re and
+// im), so the sums depend on the data alone, not on a plan's chain count or
+// sweep shape.  Run once per data tensor (gs_data_moments).
+template <int F>
+__global__ __launch_bounds__(64) void k_data_moments(int L, const double* __restrict__ d, double* __restrict__ mom) {
+    constexpr int ND = SweepAcc<F>::ND;
+    const int ell = blockIdx.x * blockDim.x + threadIdx.x;
+    if (ell > L) return;
+    const long long NR = (long long)(L + 1) * (L + 1);
+    double a[ND];
+#pragma unroll
+    for (int q = 0; q < ND; ++q) a[q] = 0.0;
+    for (int m = 0; m <= ell; ++m) {
+        const long long i = (long long)m * (2 * L + 1 - m) / 2 + ell;
+        const long long r = m == 0 ? (long long)ell : 2 * i - (L + 1);
+        const int nv = m == 0 ? 1 : 2;
+        for (int c = 0; c < nv; ++c) {
+            double dv[F];
+#pragma unroll
+            for (int f = 0; f < F; ++f) dv[f] = d[f * NR + r + c];
+            if constexpr (F == 3) {
+                a[0] += dv[0] * dv[0];
+                a[1] += dv[0] * dv[1];
+                a[2] += dv[1] * dv[1];
+                a[3] += dv[2] * dv[2];
+            } else {
+#pragma unroll
+                for (int f = 0; f < F; ++f) a[f] += dv[f] * dv[f];
+            }
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < ND; ++q) mom[q * (L + 1) + ell] = a[q];
+}
+
+// the statistics of s = P d + Q z from the raw moments (R: SweepAcc<F>::NRAW sums
+// of z z^T and d z^T, A: the data moments) and the operator pm of this (chain, l):
+//   sum s s^T = P A P^T + P C Q^T + Q C^T P^T + Q Z Q^T,   sum d s^T = A P^T + C Q^T
+// A zero operator gives exactly +0 in every row.
+template <int F>
+__device__ __forceinline__ void raw_to_stats(const double (&R)[SweepAcc<F>::NRAW], const double (&A)[SweepAcc<F>::ND],
+                                             const double (&pm)[NP], double (&st)[SweepAcc<F>::NS]) {
+    if constexpr (F == 3) {
+        const double Z00 = R[0], Z01 = R[1], Z11 = R[2], Z22 = R[3];
+        const double C00 = R[4], C10 = R[5], C01 = R[6], C11 = R[7], C22 = R[8];   // C_ij = sum d_i z_j
+        const double A00 = A[0], A01 = A[1], A11 = A[2], A22 = A[3];
+        const double p0 = pm[0], p1 = pm[1], p2 = pm[2], p3 = pm[3], p4 = pm[4];
+        const double q00 = pm[5], q10 = pm[6], q11 = pm[7], q22 = pm[8];
+        // s0 = u0 + v0, s1 = u1 + v1 with u = P d (rows 0, 1), v0 = q00 z0, v1 = q10 z0 + q11 z1
+        const double u0c0 = p0 * C00 + p1 * C10;      // sum u0 z0
+        const double u0c1 = p0 * C01 + p1 * C11;      // sum u0 z1
+        const double u1c0 = p2 * C00 + p3 * C10;      // sum u1 z0
+        const double u1c1 = p2 * C01 + p3 * C11;      // sum u1 z1
+        const double u0u0 = p0 * p0 * A00 + 2.0 * (p0 * p1) * A01 + p1 * p1 * A11;
+        const double u1u1 = p2 * p2 * A00 + 2.0 * (p2 * p3) * A01 + p3 * p3 * A11;
+        const double u0u1 = p0 * p2 * A00 + (p0 * p3 + p1 * p2) * A01 + p1 * p3 * A11;
+        st[0] = u0u0 + 2.0 * (q00 * u0c0) + q00 * q00 * Z00;
+        st[1] = u1u1 + 2.0 * (q10 * u1c0 + q11 * u1c1) + (q10 * q10 * Z00 + 2.0 * (q10 * q11) * Z01 + q11 * q11 * Z11);
+        st[2] = p4 * p4 * A22 + 2.0 * (p4 * q22) * C22 + q22 * q22 * Z22;
+        st[3] = u0u1 + (q10 * u0c0 + q11 * u0c1) + q00 * u1c0 + q00 * (q10 * Z00 + q11 * Z01);
+        st[4] = p0 * A00 + p1 * A01 + q00 * C00;
+        st[5] = p0 * A01 + p1 * A11 + q00 * C10;
+        st[6] = p2 * A01 + p3 * A11 + q10 * C10 + q11 * C11;
+        st[7] = p4 * A22 + q22 * C22;
+    } else {
+#pragma unroll
+        for (int f = 0; f < F; ++f) {
+            const double P = pm[f], Q = pm[F + f];
+            st[f] = P * P * A[f] + 2.0 * (P * Q) * R[F + f] + Q * Q * R[f];
+            st[F + f] = P * A[f] + Q * R[F + f];
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < SweepAcc<F>::NS; ++q) st[q] += 0.0;     // -0 -> +0
+}
+
+// The statistics finish of a raw-moment sweep (native-draw NC steps).  One
+// workgroup per (chain, l tile) holds every raw sum of its 64 l: wave w adds
+// chunks w, w + 4, ... in order, the four wave sums are added in wave order
+// (the order of k_stats_finish, whatever the chain or GPU count), then wave 0
+// computes the NC operator of its (chain, l) from the chain's D_l -- the code
+// and bits of the parameter table and of the in-sweep operator -- and writes
+// the statistic rows the MH reads.  nblk_prop + nblk_u workgroups in front:
+// the step's deferred MH proposals and accept uniforms, as k_stats_finish_pro.
+template <int F>
+__global__ __launch_bounds__(256) void k_stats_finish_raw(int L, int nchains, int ntile, int nchunkg, int tm,
+                                                          const double* __restrict__ partials,
+                                                          const double* __restrict__ dmom, double* __restrict__ stats,
+                                                          SweepOp op, int nblk_prop, int nblk_u,
+                                                          double* __restrict__ u_out, int nspec, int nacc,
+                                                          int n_iter_mh, const int* __restrict__ nbins_arr,
+                                                          const double* __restrict__ prop_sd,
+                                                          const double* __restrict__ pro_dl, double* __restrict__ prop,
+                                                          double* __restrict__ logr, uint32_t seed_lo,
+                                                          uint32_t seed_hi, IterArg itarg, int chain0,
+                                                          double* __restrict__ snap) {
+    constexpr int NRAW = SweepAcc<F>::NRAW, ND = SweepAcc<F>::ND, NS = SweepAcc<F>::NS;
+    const int bx = (int)blockIdx.x;
+    if (bx < nblk_prop) {
+        mh_propose_at<F>(bx * (long long)blockDim.x + threadIdx.x, nchains, op.maxbins, nbins_arr, prop_sd, pro_dl,
+                         prop, logr, nullptr, seed_lo, seed_hi, itarg, chain0, snap);
+        return;
+    }
+    if (bx < nblk_prop + nblk_u) {
+        mh_uniform_at((bx - nblk_prop) * (long long)blockDim.x + threadIdx.x, nchains, nspec, nbins_arr, nacc,
+                      n_iter_mh, seed_lo, seed_hi, itarg.get(), chain0, u_out);
+        return;
+    }
+    const int b = bx - nblk_prop - nblk_u;
+    const int t = b % ntile;
+    const int chain = b / ntile;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int Lp1 = L + 1;
+    GS_ASSERT(chain < nchains);
+    const int ell = L - WAVE * t - 63 + lane;
+    // wave 0: the operator's inputs and the data moments ahead of the partial sums
+    double pm[NP], A[ND];
+    if (w == 0) {
+        const int lc = max(ell, 0);
+        block_params_compute<F, GS_MODE_NONCENTERED>(chain, lc, L, op.maxbins, op.dl, op.ell2bin, op.bl, op.k0, op.k1,
+                                                     op.k2, pm);
+#pragma unroll
+        for (int q = 0; q < ND; ++q) A[q] = dmom[q * Lp1 + lc];
+    }
+    const int cmax = (L - WAVE * t) / tm;               // last chunk of tile t
+    GS_ASSERT(cmax < nchunkg);
+    const double* pp = partials + ((long long)chain * ntile + t) * nchunkg * NRAW * WAVE + lane;
+    const long long cs = (long long)NRAW * WAVE;
+    double acc[NRAW];
+#pragma unroll
+    for (int q = 0; q < NRAW; ++q) acc[q] = 0.0;
+    int c = w;
+    for (; c + 4 <= cmax; c += 8) {                     // two chunks' loads in flight
+        double v0[NRAW], v1[NRAW];
+#pragma unroll
+        for (int q = 0; q < NRAW; ++q) v0[q] = pp[c * cs + q * WAVE];
+#pragma unroll
+        for (int q = 0; q < NRAW; ++q) v1[q] = pp[(c + 4) * cs + q * WAVE];
+#pragma unroll
+        for (int q = 0; q < NRAW; ++q) acc[q] += v0[q];
+#pragma unroll
+        for (int q = 0; q < NRAW; ++q) acc[q] += v1[q];
+    }
+    for (; c <= cmax; c += 4)
+#pragma unroll
+        for (int q = 0; q < NRAW; ++q) acc[q] += pp[c * cs + q * WAVE];
+    __shared__ double red[3][NRAW][WAVE];
+    if (w > 0)
+#pragma unroll
+        for (int q = 0; q < NRAW; ++q) red[w - 1][q][lane] = acc[q];
+    __syncthreads();
+    if (w == 0 && ell >= 0) {
+        double R[NRAW], st[NS];
+#pragma unroll
+        for (int q = 0; q < NRAW; ++q) R[q] = ((acc[q] + red[0][q][lane]) + red[1][q][lane]) + red[2][q][lane];
+        raw_to_stats<F>(R, A, pm, st);
+#pragma unroll
+        for (int q = 0; q < NS; ++q) stats[((long long)chain * NS + q) * Lp1 + ell] = st[q];
     }
 }
 
@@ -2079,7 +2300,7 @@ __global__ void k_record_trace(long long n, const double* __restrict__ dl, doubl
 // ============================================================================
 // the library options (gs_option_set): a fixed set of names
 static const char* const k_options[] = {
-    "GS_SWEEP_TW", "GS_SWEEP_THROUGHPUT", "GS_MH_SPLIT", "GS_CLS_PRE", "GS_CLS_PRE_MANY", "GS_F2_GROUP_BYTES",
+    "GS_SWEEP_TW", "GS_SWEEP_THROUGHPUT", "GS_NC_RAW", "GS_MH_SPLIT", "GS_CLS_PRE", "GS_CLS_PRE_MANY", "GS_F2_GROUP_BYTES",
     "GS_F2_BATCH_BYTES", "GS_SHT_LDS_FFT_MAX", "GS_SHT_SEG", "GS_SHT_SYN", "GS_SHT_ANA", "GS_SHT_MERGE_RINGS",
     "GS_SHT_CONST_RINGS", "GS_SHT_BLOCKS_MFMA", "GS_SHT_BLK_STAGE", "GS_SHT_FUSED_AUX", "GS_SHT_MFMA_MAX_GB",
     "GS_SHT_RING_TW2"};
@@ -2376,7 +2597,13 @@ int gs_plan_create(const gs_model_desc* desc, gs_plan** out) {
     p->inkernel_params = p->nchains <= 4;
     p->sweep_latency = gs_detail::option("GS_SWEEP_THROUGHPUT") == nullptr;
     const size_t nc = (size_t)p->nchains;
-    rc |= dev_alloc(&p->partials, nc * p->ntile * p->nchunkg * p->nstat * WAVE);
+    {
+        const char* e = gs_detail::option("GS_NC_RAW");
+        p->raw_on = e ? std::atoi(e) != 0 : true;
+    }
+    const int nraw = F == 3 ? 9 : 2 * F, ndm = F == 3 ? 4 : F;
+    rc |= dev_alloc(&p->partials, nc * p->ntile * p->nchunkg * std::max(p->nstat, nraw) * WAVE);
+    rc |= dev_alloc(&p->dmom, (size_t)ndm * (L + 1));
     rc |= dev_alloc(&p->params, nc * (L + 1) * NP);
     rc |= dev_alloc(&p->stats, nc * p->nstat * (L + 1));
     rc |= dev_alloc(&p->prop, nc * p->nspec * maxbins);
@@ -2401,7 +2628,7 @@ int gs_plan_create(const gs_model_desc* desc, gs_plan** out) {
 int gs_plan_destroy(gs_plan* p) {
     if (!p) return 0;
     void* bufs[] = {p->iter_dev, p->ell2blk, p->gbuf, p->phase_tab, p->phase_rng, p->meta, p->bl, p->ell2bin, p->bins, p->blocks, p->prop_sd, p->tasks, p->partials, p->u_nat,
-                    p->params, p->stats, p->prop, p->logr, p->dl_tmp, p->cls_var, p->phase_tab_s, p->phase_rng_s};
+                    p->params, p->stats, p->prop, p->logr, p->dl_tmp, p->cls_var, p->phase_tab_s, p->phase_rng_s, p->dmom};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     for (hipEvent_t e : p->ev) (void)hipEventDestroy(e);
@@ -2547,6 +2774,29 @@ static int timing_begin(gs_plan* p, hipStream_t s, hipEvent_t* e0, hipEvent_t* e
 
 static int stats_finish(gs_plan* p, double* stats, void* stream) {
     const long long n = (long long)p->nchains * p->nstat * p->ntile;
+    if (p->raw_pending) {
+        // raw sums: one workgroup per (chain, tile) sums them and applies the NC
+        // operator of the sweep's D_l; the prologue's deferred draws ride in front
+        p->raw_pending = false;
+        const bool pro = p->pro_pending;
+        p->pro_pending = false;
+        const int nbp = pro ? nblk((long long)p->nchains * p->nspec * p->maxbins, 256) : 0;
+        const int nbu = pro && p->u_nat_ready ? nblk((long long)p->nchains * p->nacc, 256) : 0;
+        const int tmf = p->rows_per_task * (4 / p->sweep_tw);
+        const long long nr = (long long)p->nchains * p->ntile;
+        const SweepOp op{GS_MODE_NONCENTERED, p->maxbins, p->raw_dl, p->ell2bin, p->bl, p->kappa[0], p->kappa[1],
+                         p->kappa[2]};
+#define GS_FR(FF) hipLaunchKernelGGL((k_stats_finish_raw<FF>), dim3((unsigned)(nr + nbp + nbu)), dim3(256), 0,          \
+                                     S(stream), p->L, p->nchains, p->ntile, p->nchunkg, tmf, p->partials, p->dmom,      \
+                                     stats, op, nbp, nbu, p->u_nat, p->nspec, p->nacc, p->n_iter_mh, p->meta,           \
+                                     p->prop_sd, p->pro_dl, p->prop, p->logr, p->pro_slo, p->pro_shi,                   \
+                                     p->ita(p->pro_it), p->chain0, p->dl_tmp)
+        if (p->F == 1) GS_FR(1); else if (p->F == 2) GS_FR(2); else GS_FR(3);
+#undef GS_FR
+        GS_LAUNCH_CHECK("k_stats_finish_raw");
+        if (pro) p->snap_ok = true;
+        return 0;
+    }
     if (p->pro_pending) {
         // the prologue's deferred draws in front of the partial sums
         p->pro_pending = false;
@@ -2579,10 +2829,15 @@ static int stats_finish(gs_plan* p, double* stats, void* stream) {
 static int sweep_launch(gs_plan* p,const double* d_alm, const double* params, const double* z, uint64_t seed,
                         uint32_t iteration, uint32_t substep, double* s_out, double* stats, bool given,
                         void* stream, bool finish = true, int pmode = -1, const double* dl = nullptr,
-                        bool* cls_pre_done = nullptr) {
+                        bool* cls_pre_done = nullptr, bool raw = false) {
     if (check_plan(p)) return -1;
-    if (!d_alm || !stats || (!given && !params && pmode < 0) || (given && !s_out) || (pmode >= 0 && !dl))
+    // raw: native NC draws accumulating raw moments (dl: the D_l the finish applies)
+    const bool raw_nost = raw && !s_out;        // no operator anywhere in the sweep
+    if (!d_alm || !stats || (!given && !params && pmode < 0 && !raw_nost) || (given && !s_out) ||
+        ((pmode >= 0 || raw) && !dl) || (raw && (given || z)))
         return set_error("gs_cr_sweep: null argument");
+    p->raw_pending = raw;
+    p->raw_dl = raw ? dl : nullptr;
     const SweepOp op{pmode, p->maxbins, dl, p->ell2bin, p->bl, p->kappa[0], p->kappa[1], p->kappa[2]};
     const uint32_t slo = (uint32_t)(seed & 0xFFFFFFFFu), shi = (uint32_t)(seed >> 32);
     const int nlog = (int)((long long)p->nchains * p->npair);
@@ -2608,9 +2863,15 @@ static int sweep_launch(gs_plan* p,const double* d_alm, const double* params, co
                                           p->nchunkg, p->rows_per_task, p->sweep_tw, p->tasks, d_alm, params, z,    \
                                           s_out, p->partials, slo, shi, p->ita(iteration), substep, p->chain0, op, cp, \
                                           ProPre{}, nlog)
-#define GS_SWL2(FF) do { if (st) GS_SWL(FF, true); else GS_SWL(FF, false); } while (0)
+#define GS_SWLR(FF, SS) hipLaunchKernelGGL((k_cr_sweep<FF, 0, SS, 4, true>), g, b, 0, S(stream), p->L, p->nchains,      \
+                                           p->ntile, p->nchunkg, p->rows_per_task, p->sweep_tw, p->tasks, d_alm, params, \
+                                           z, s_out, p->partials, slo, shi, p->ita(iteration), substep, p->chain0, op,   \
+                                           cp, ProPre{}, nlog)
+#define GS_SWL2(FF) do { if (raw && st) GS_SWLR(FF, true); else if (raw) GS_SWLR(FF, false);                            \
+                         else if (st) GS_SWL(FF, true); else GS_SWL(FF, false); } while (0)
         if (p->F == 1) GS_SWL2(1); else if (p->F == 2) GS_SWL2(2); else GS_SWL2(3);
 #undef GS_SWL2
+#undef GS_SWLR
 #undef GS_SWL
         GS_LAUNCH_CHECK("k_cr_sweep");
         if (p->timing && record_ev(e1, S(stream))) return -1;
@@ -2642,11 +2903,17 @@ static int sweep_launch(gs_plan* p,const double* d_alm, const double* params, co
                                              s_out,                                                                   \
                                              p->partials, slo, shi, p->ita(iteration), substep, p->chain0, \
                                              op, none, pp, nlog)
+#define GS_SWR(FF, SS) hipLaunchKernelGGL((k_cr_sweep<FF, 0, SS, 0, true>), g, b, 0, S(stream), p->L, p->nchains,       \
+                                          p->ntile, p->nchunkg, p->rows_per_task, p->sweep_tw, p->tasks, d_alm, params,  \
+                                          z, s_out, p->partials, slo, shi, p->ita(iteration), substep, p->chain0, op,    \
+                                          none, pp, nlog)
 #define GS_SWF(FF) do { if (given) GS_SW(FF, 2, false); else if (rep && st) GS_SW(FF, 1, true); \
-                        else if (rep) GS_SW(FF, 1, false); else if (st) GS_SW(FF, 0, true);            \
+                        else if (rep) GS_SW(FF, 1, false); else if (raw && st) GS_SWR(FF, true);      \
+                        else if (raw) GS_SWR(FF, false); else if (st) GS_SW(FF, 0, true);             \
                         else GS_SW(FF, 0, false); } while (0)
     if (p->F == 1) GS_SWF(1); else if (p->F == 2) GS_SWF(2); else GS_SWF(3);
 #undef GS_SWF
+#undef GS_SWR
 #undef GS_SW
     GS_LAUNCH_CHECK("k_cr_sweep");
     if (p->timing && record_ev(e1, S(stream))) return -1;
@@ -2936,6 +3203,13 @@ int gs_nc_prologue(gs_plan* p, const double* dl, const double* u_prop, uint64_t 
         p->pro_pending = true;
         p->pro_dl = dl; p->pro_slo = slo; p->pro_shi = shi; p->pro_it = it;
         if (nbq == 0) return 0;                   // the sweep computes the operator: no launch
+        if (p->raw_on) {
+            // the parameter table waits for gs_nc_sweep: a raw-moment sweep that
+            // stores no map reads no operator, and the step has no prologue launch
+            p->par_pending = true;
+            p->par_dl = dl;
+            return 0;
+        }
 #define GS_PRQ(FF) hipLaunchKernelGGL((k_nc_prologue<FF>), dim3(nbq), dim3(256), 0, S(stream), 0, nbq, p->u_nat,     \
                                       p->nspec, p->nacc, p->n_iter_mh, p->L, p->nchains, p->maxbins, p->ell2bin, p->bl, \
                                       p->kappa[0], p->kappa[1], p->kappa[2], p->params, p->meta, p->prop_sd, dl,        \
@@ -2946,6 +3220,7 @@ int gs_nc_prologue(gs_plan* p, const double* dl, const double* u_prop, uint64_t 
         return 0;
     }
     p->pro_pending = false;
+    p->par_pending = false;
 #define GS_PRO(FF) hipLaunchKernelGGL((k_nc_prologue<FF>), dim3(nbp + nbq + nbu), dim3(256), 0, S(stream), nbp, nbq,   \
                                       p->u_nat, p->nspec, p->nacc, p->n_iter_mh, p->L,                                  \
                                       p->nchains, p->maxbins, p->ell2bin, p->bl, p->kappa[0], p->kappa[1], p->kappa[2], \
@@ -2958,19 +3233,56 @@ int gs_nc_prologue(gs_plan* p, const double* dl, const double* u_prop, uint64_t 
     return 0;
 }
 
+static int data_moments_launch(gs_plan* p, const double* d_alm, void* stream) {
+#define GS_DM(FF) hipLaunchKernelGGL((k_data_moments<FF>), dim3(nblk(p->L + 1, 64)), dim3(64), 0, S(stream), p->L, d_alm, \
+                                     p->dmom)
+    if (p->F == 1) GS_DM(1); else if (p->F == 2) GS_DM(2); else GS_DM(3);
+#undef GS_DM
+    GS_LAUNCH_CHECK("k_data_moments");
+    p->dmom_src = d_alm;
+    return 0;
+}
+
+int gs_data_moments(gs_plan* p, const double* d_alm, void* stream) {
+    if (check_plan(p)) return -1;
+    if (!d_alm) return set_error("gs_data_moments: null argument");
+    return data_moments_launch(p, d_alm, stream);
+}
+
 int gs_nc_sweep(gs_plan* p, const double* d_alm, const double* dl, double* s_out, const double* z, uint64_t seed,
                 uint32_t it, int finish, void* stream) {
     if (check_plan(p)) return -1;
-    if (!dl) return set_error("gs_nc_sweep: null argument");
+    if (!dl || !d_alm) return set_error("gs_nc_sweep: null argument");
+    // native draws: raw moments, the operator applied by the statistics finish
+    const bool raw = p->raw_on && z == nullptr;
+    if (raw && p->dmom_src != d_alm && data_moments_launch(p, d_alm, stream)) return -1;
+    if (p->par_pending) {
+        // the prologue's parameter table of this step, if this sweep reads it
+        p->par_pending = false;
+        if (!(raw && !s_out)) {
+            if (p->par_dl != dl) return set_error("gs_nc_sweep: D_l differs from the prologue's");
+            if (gs_block_params(p, GS_MODE_NONCENTERED, dl, p->params, stream)) return -1;
+        }
+    }
     if (p->inkernel_params)
         return sweep_launch(p, d_alm, nullptr, z, seed, it, 0, s_out, p->stats, false, stream, finish != 0,
-                            GS_MODE_NONCENTERED, dl);
-    return sweep_launch(p, d_alm, p->params, z, seed, it, 0, s_out, p->stats, false, stream, finish != 0);
+                            GS_MODE_NONCENTERED, dl, nullptr, raw);
+    return sweep_launch(p, d_alm, p->params, z, seed, it, 0, s_out, p->stats, false, stream, finish != 0, -1, dl,
+                        nullptr, raw);
 }
 
 int gs_nc_finish(gs_plan* p, void* stream) {
     if (check_plan(p)) return -1;
     return stats_finish(p, p->stats, stream);
+}
+
+int gs_nc_stats(gs_plan* p, double* stats_out, void* stream) {
+    if (check_plan(p)) return -1;
+    if (!stats_out) return set_error("gs_nc_stats: null argument");
+    if (p->raw_pending) return set_error("gs_nc_stats: the statistics wait for gs_nc_finish");
+    GS_CHECK(hipMemcpyAsync(stats_out, p->stats, sizeof(double) * p->nchains * p->nstat * (p->L + 1),
+                            hipMemcpyDeviceToDevice, S(stream)));
+    return 0;
 }
 
 int gs_nc_decide(gs_plan* p, double* dl, const double* u_acc, uint64_t seed, uint32_t it, int32_t* accept_out,

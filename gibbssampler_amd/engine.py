@@ -249,6 +249,11 @@ class GibbsPlan:
                                              C.ptr(u_acc), int(seed), int(iteration), C.ptr(accept), self._s()),
                 "gs_step_noncentered")
 
+    def data_moments(self, d):
+        """Per-l moments of the data tensor d for the raw-moment NC statistics
+        (gs_data_moments): once per tensor, and again after changing d in place."""
+        C.check(self.lib.gs_data_moments(self._h, C.ptr(d), self._s()), "gs_data_moments")
+
     # the three stages of step_noncentered (for pipelined schedules)
     def nc_prologue(self, dl, u_prop=None, seed=0, iteration=0):
         C.check(self.lib.gs_nc_prologue(self._h, C.ptr(dl), C.ptr(u_prop), int(seed), int(iteration), self._s()),
@@ -260,6 +265,12 @@ class GibbsPlan:
 
     def nc_finish(self):
         C.check(self.lib.gs_nc_finish(self._h, self._s()), "gs_nc_finish")
+
+    def nc_stats(self, out=None):
+        """The statistic rows [nchains, nstat, L+1] of the last NC sweep (what the MH reads)."""
+        out = self.zeros(self.nchains, self.nstat, self.L + 1) if out is None else out
+        C.check(self.lib.gs_nc_stats(self._h, C.ptr(out), self._s()), "gs_nc_stats")
+        return out
 
     def nc_decide(self, dl, u_acc=None, seed=0, iteration=0, accept=None):
         C.check(self.lib.gs_nc_decide(self._h, C.ptr(dl), C.ptr(u_acc), int(seed), int(iteration), C.ptr(accept),

@@ -66,6 +66,8 @@ class BatchedRunner:
                               n_iter_metropolis=n_iter_metropolis)
         p = self.plan
         self.d = p.data_tensor(d_alm)
+        if kind == "noncentered" and rng == "native":
+            p.data_moments(self.d)
         self.s = p.zeros(p.nchains, p.F, p.NR) if store_skymap else None
         self.dl = None
         self.dl_tmp = p.zeros(p.nchains, p.nspec, p.maxbins)

@@ -186,11 +186,29 @@ int gs_step_noncentered(gs_plan* plan, const double* d_alm, double* dl_binned, d
  * in the prologue (the same values either way). */
 int gs_nc_prologue(gs_plan* plan, const double* dl_binned, const double* u_prop_replay, uint64_t seed,
                    uint32_t iteration, void* stream);
+/* Raw-moment statistics (native draws; option GS_NC_RAW=0 at plan creation turns
+ * them off).  The NC draw is s = P d + Q z with P, Q the operator of the chain's
+ * D_l, so the per-l statistics sum s s^T and sum d s^T follow from the
+ * state-independent moments sum z z^T, sum d z^T and sum d d^T.  gs_nc_sweep
+ * with z_replay NULL accumulates the first two (it reads no operator unless
+ * s_out is given), and the statistics finish applies the operator of dl_binned
+ * to them and to the data moments; the step then has no parameter launch unless
+ * the map is stored.
+ * gs_data_moments computes sum_m d d^T per l of the data tensor d_alm
+ * [nfields][(lmax+1)^2] into the plan and remembers the pointer.  Call it once
+ * per data tensor.  gs_nc_sweep makes the call itself when it is handed a
+ * pointer other than the remembered one, but it cannot see an in-place change:
+ * after writing new values into the same d_alm buffer, call gs_data_moments
+ * again before the next step. */
+int gs_data_moments(gs_plan* plan, const double* d_alm, void* stream);
 int gs_nc_sweep(gs_plan* plan, const double* d_alm, const double* dl_binned, double* s_out, const double* z_replay,
                 uint64_t seed, uint32_t iteration, int finish, void* stream);
 /* finish = 0 leaves the statistics as per-task partials; gs_nc_finish reduces them
  * (fixed order) -- lets a caller bracket the sweep kernel alone with timing events */
 int gs_nc_finish(gs_plan* plan, void* stream);
+/* copies the statistics the last gs_nc_sweep / gs_nc_finish reduced (the rows the
+ * MH reads) to stats_out [nchains][nstat][lmax+1] */
+int gs_nc_stats(gs_plan* plan, double* stats_out, void* stream);
 int gs_nc_decide(gs_plan* plan, double* dl_binned, const double* u_accept_replay, uint64_t seed, uint32_t iteration,
                  int32_t* accept_out, void* stream);
 /* gs_nc_decide with the step's bookkeeping fused into the same launch (native

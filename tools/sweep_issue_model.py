@@ -19,7 +19,7 @@ import tempfile
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-KERNEL = r"_Z10k_cr_sweepILi3ELi0ELb0ELi0EE"
+KERNEL = r"_Z10k_cr_sweepILi3ELi0ELb0ELi0ELb1EE"      # <F 3, native, no map, throughput form, raw moments>
 
 # opcode (prefix) -> the microbench class whose W=8 rate prices it
 CLASS = [
