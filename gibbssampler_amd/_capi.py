@@ -91,6 +91,11 @@ _SIGS = [
     ("gs_sweep_stats", ctypes.c_int, [_VP, _VP, _VP, _VP, _VP]),
     ("gs_cls_draw", ctypes.c_int, [_VP, _VP, _VP, ctypes.c_uint64, ctypes.c_uint32, _VP, _VP]),
     ("gs_nc_mh", ctypes.c_int, [_VP, _VP, _VP, _VP, _VP, ctypes.c_uint64, ctypes.c_uint32, _VP, _VP]),
+    ("gs_mh_adapt_enable", ctypes.c_int, [_VP, ctypes.c_double, ctypes.c_double]),
+    ("gs_mh_adapt", ctypes.c_int, [_VP, _VP, _VP]),
+    ("gs_mh_scale_get", ctypes.c_int, [_VP, _VP, _VP, _VP]),
+    ("gs_mh_scale_set", ctypes.c_int, [_VP, _VP, _VP, _VP]),
+    ("gs_mh_proposal_sd", ctypes.c_int, [_VP, _VP, _VP]),
     ("gs_stats_to_noncentered", ctypes.c_int, [_VP, _VP, _VP, _VP]),
     ("gs_recentre", ctypes.c_int, [_VP, _VP, _VP, _VP, _VP]),
     ("gs_step_centered", ctypes.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, ctypes.c_uint64, ctypes.c_uint32, _VP]),

@@ -56,6 +56,32 @@ class GibbsConfig:
         self.proposal_variances_nc_polarized = proposal_variances(L, self.NSIDE, self.bins, self.bl_gauss,
                                                                   self.noise_covar_pol, self.noise_covar_temp)
 
+        self.starting_point = None                             # config.py:205-207
+
+    def use_preliminary(self, tuned_variances, starting_point):
+        """The production half of config.py:161-225 (preliminary_run = False)
+        from a preliminary run's results handed over in memory -- no scan of a
+        scratch directory, no hand-set scale factors: tuned_variances is a
+        sampler's ``tuned_proposal_variances`` after a run with n_warmup > 0
+        (per spectrum nbins-2 values), starting_point the last row of its D_l
+        history (per spectrum nbins values, one chain)."""
+        pv, sp = {}, {}
+        for s, b in self.bins.items():
+            nb = len(b) - 1
+            v = np.array(tuned_variances[s], dtype=np.float64)
+            x = np.array(starting_point[s], dtype=np.float64)
+            if v.shape != (nb - 2,):
+                raise ValueError(f"tuned_variances[{s}] must have nbins-2 = {nb - 2} entries")
+            if x.shape != (nb,):
+                raise ValueError(f"starting_point[{s}] must have nbins = {nb} entries (one chain's last D_l row)")
+            if not (np.all(np.isfinite(v)) and np.all(v > 0)):
+                raise ValueError(f"tuned_variances[{s}] must be finite and positive")
+            pv[s], sp[s] = v, x
+        self.proposal_variances_nc_polarized = pv
+        self.starting_point = sp
+        self.preliminary_run = False
+        return self
+
     def compute_init_values_pol(self, unbinned_vars, pol):
         """config.py:93-104."""
         b = self.bins[pol]

@@ -89,6 +89,20 @@ struct gs_plan {
     int* bins = nullptr;             // [nspec][maxbins+1]
     int* blocks = nullptr;           // [nspec][maxbins+1] (clipped edges)
     double* prop_sd = nullptr;       // [nspec][maxbins]
+    // warm-up adaptation of the proposal scales (gs_mh_adapt_enable): per chain
+    // and MH block a log-scale and a step count, block j = accept offset / n_iter_mh
+    // (the order of the accept flags), and the chain's own table
+    // sd = prop_sd * exp(log-scale of the bin's block), always written by k_mh_sd_expand
+    bool adapt_on = false;
+    double adapt_target = 0.25, adapt_kappa = 0.6, adapt_lmax = 20.0;
+    int nblk_mh = 0;                 // MH blocks per chain (nacc / n_iter_mh)
+    std::vector<int> bin2blk_h;      // [nspec][maxbins] block j of each bin (-1: none)
+    int* bin2blk = nullptr;
+    double* mh_lam = nullptr;        // [nchains][nblk_mh]
+    int* mh_cnt = nullptr;           // [nchains][nblk_mh]
+    double* sd_chain = nullptr;      // [nchains][nspec][maxbins]
+    int sd_stride = 0;               // 0: every chain reads prop_sd
+    const double* sd_tab() const { return adapt_on ? sd_chain : prop_sd; }
     int* meta = nullptr;             // [16]: nbins[4], nblocks[4], acc_off[4], mh_order[4]
     int2* tasks = nullptr;           // [npair] (tile group, row chunk) of the CR sweep
     int npair = 0, ntile = 0, nchunk = 0, rows_per_task = 64;
@@ -601,6 +615,7 @@ struct ProPre {
     int nspec = 0, nacc = 0, n_iter_mh = 0, maxbins = 0;
     const int* nbins = nullptr;      // plan meta (nbins per spectrum, blocks, accept offsets)
     const double* prop_sd = nullptr;
+    int sd_stride = 0;               // per-chain stride of prop_sd (0: one shared table)
     const double* dl = nullptr;
     double* prop = nullptr;
     double* logr = nullptr;
@@ -1148,7 +1163,8 @@ __device__ __forceinline__ double wave_sum(double v) {
 // (313-330, 410-413): one thread per (chain, spectrum, bin)
 template <int F>
 __device__ __forceinline__ void mh_propose_at(long long g, int nchains, int maxbins, const int* __restrict__ nbins_arr,
-                                              const double* __restrict__ prop_sd, const double* __restrict__ dl,
+                                              const double* __restrict__ prop_sd, int sd_stride,
+                                              const double* __restrict__ dl,
                                               double* __restrict__ prop, double* __restrict__ logr,
                                               const double* __restrict__ u_prop, uint32_t seed_lo,
                                               uint32_t seed_hi, IterArg itarg, int chain0,
@@ -1163,7 +1179,8 @@ __device__ __forceinline__ void mh_propose_at(long long g, int nchains, int maxb
     const int chain = (int)(g / ((long long)maxbins * NSP));
     if (b < 2 || b >= nbins_arr[sp]) return;
     const Key key = chain_key(seed_lo, seed_hi, (uint32_t)(chain0 + chain));
-    const double sd = prop_sd[sp * maxbins + b];
+    // sd_stride 0: the plan's shared table; nspec * maxbins: the chain's own rows (gs_mh_adapt_enable)
+    const double sd = prop_sd[chain * sd_stride + sp * maxbins + b];
     const double old = dl[g];
     double p, lr;
     if (F == 3 && sp == 3) {
@@ -1183,13 +1200,47 @@ __device__ __forceinline__ void mh_propose_at(long long g, int nchains, int maxb
 
 template <int F>
 __global__ __launch_bounds__(256) void k_mh_propose(int nchains, int maxbins, const int* __restrict__ nbins_arr,
-                                                    const double* __restrict__ prop_sd, const double* __restrict__ dl,
+                                                    const double* __restrict__ prop_sd, int sd_stride,
+                                                    const double* __restrict__ dl,
                                                     double* __restrict__ prop, double* __restrict__ logr,
                                                     const double* __restrict__ u_prop, uint32_t seed_lo,
                                                     uint32_t seed_hi, IterArg itarg, int chain0,
                                                     double* __restrict__ snap) {
-    mh_propose_at<F>(blockIdx.x * (long long)blockDim.x + threadIdx.x, nchains, maxbins, nbins_arr, prop_sd, dl, prop,
-                     logr, u_prop, seed_lo, seed_hi, itarg, chain0, snap);
+    mh_propose_at<F>(blockIdx.x * (long long)blockDim.x + threadIdx.x, nchains, maxbins, nbins_arr, prop_sd, sd_stride,
+                     dl, prop, logr, u_prop, seed_lo, seed_hi, itarg, chain0, snap);
+}
+
+// Warm-up adaptation of the proposal scales, first launch: one thread per
+// (chain, MH block) reads its own log-scale only, so no thread sees another's
+// update.  abar: the share of the block's n_iter_mh attempts accepted this step;
+//   n <- n + 1,  lam <- clamp(lam + n^-kappa (abar - target), -lmax, lmax)
+__global__ __launch_bounds__(256) void k_mh_adapt_update(int nchains, int nblk, int n_iter_mh,
+                                                         const int32_t* __restrict__ accept,
+                                                         double* __restrict__ lam, int* __restrict__ cnt,
+                                                         double target, double kappa, double lmax) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= nchains * nblk) return;
+    int na = 0;
+    for (int a = 0; a < n_iter_mh; ++a) na += accept[(long long)g * n_iter_mh + a] != 0;
+    const double abar = (double)na / (double)n_iter_mh;
+    const int n = cnt[g] + 1;
+    const double step = pow((double)n, -kappa) * (abar - target);   // its own statement: rounded before the add
+    const double v = lam[g] + step;
+    cnt[g] = n;
+    lam[g] = fmin(fmax(v, -lmax), lmax);
+}
+
+// second launch (and gs_mh_scale_set / gs_mh_adapt_enable): the chain's table
+// from the log-scales, one thread per (chain, spectrum, bin) through the
+// bin-to-block table -- the only code that writes sd_chain
+__global__ __launch_bounds__(256) void k_mh_sd_expand(int nchains, int nsb, int nblk, const int* __restrict__ bin2blk,
+                                                      const double* __restrict__ sd0, const double* __restrict__ lam,
+                                                      double* __restrict__ sd) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= nchains * nsb) return;
+    const int chain = g / nsb, i = g % nsb;
+    const int j = bin2blk[i];
+    sd[g] = j < 0 ? sd0[i] : sd0[i] * exp(lam[chain * nblk + j]);
 }
 
 // flat accept order of the plan (same counters as k_mh_fused / k_mh_accept)
@@ -1220,15 +1271,15 @@ __global__ __launch_bounds__(256) void k_stats_finish_pro(int L, int nchains, in
                                                           double* __restrict__ u_out, int nspec, int nacc,
                                                           int n_iter_mh, int maxbins,
                                                           const int* __restrict__ nbins_arr,
-                                                          const double* __restrict__ prop_sd,
+                                                          const double* __restrict__ prop_sd, int sd_stride,
                                                           const double* __restrict__ dl, double* __restrict__ prop,
                                                           double* __restrict__ logr, uint32_t seed_lo,
                                                           uint32_t seed_hi, IterArg itarg, int chain0,
                                                           double* __restrict__ snap) {
     const int bx = (int)blockIdx.x;
     if (bx < nblk_prop) {
-        mh_propose_at<F>(bx * (long long)blockDim.x + threadIdx.x, nchains, maxbins, nbins_arr, prop_sd, dl, prop,
-                         logr, nullptr, seed_lo, seed_hi, itarg, chain0, snap);
+        mh_propose_at<F>(bx * (long long)blockDim.x + threadIdx.x, nchains, maxbins, nbins_arr, prop_sd, sd_stride, dl,
+                         prop, logr, nullptr, seed_lo, seed_hi, itarg, chain0, snap);
         return;
     }
     if (bx < nblk_prop + nblk_u) {
@@ -1347,7 +1398,7 @@ __global__ __launch_bounds__(256) void k_stats_finish_raw(int L, int nchains, in
                                                           SweepOp op, int nblk_prop, int nblk_u,
                                                           double* __restrict__ u_out, int nspec, int nacc,
                                                           int n_iter_mh, const int* __restrict__ nbins_arr,
-                                                          const double* __restrict__ prop_sd,
+                                                          const double* __restrict__ prop_sd, int sd_stride,
                                                           const double* __restrict__ pro_dl, double* __restrict__ prop,
                                                           double* __restrict__ logr, uint32_t seed_lo,
                                                           uint32_t seed_hi, IterArg itarg, int chain0,
@@ -1355,8 +1406,8 @@ __global__ __launch_bounds__(256) void k_stats_finish_raw(int L, int nchains, in
     constexpr int NRAW = SweepAcc<F>::NRAW, ND = SweepAcc<F>::ND, NS = SweepAcc<F>::NS;
     const int bx = (int)blockIdx.x;
     if (bx < nblk_prop) {
-        mh_propose_at<F>(bx * (long long)blockDim.x + threadIdx.x, nchains, op.maxbins, nbins_arr, prop_sd, pro_dl,
-                         prop, logr, nullptr, seed_lo, seed_hi, itarg, chain0, snap);
+        mh_propose_at<F>(bx * (long long)blockDim.x + threadIdx.x, nchains, op.maxbins, nbins_arr, prop_sd, sd_stride,
+                         pro_dl, prop, logr, nullptr, seed_lo, seed_hi, itarg, chain0, snap);
         return;
     }
     if (bx < nblk_prop + nblk_u) {
@@ -1421,8 +1472,8 @@ template <int F>
 __device__ void pro_pre_item(const ProPre& pp, int bx, int nchains, uint32_t seed_lo, uint32_t seed_hi, IterArg itarg,
                              int chain0) {
     if (bx < pp.nbp)
-        mh_propose_at<F>(bx * (long long)blockDim.x + threadIdx.x, nchains, pp.maxbins, pp.nbins, pp.prop_sd, pp.dl,
-                         pp.prop, pp.logr, nullptr, seed_lo, seed_hi, itarg, chain0, pp.snap);
+        mh_propose_at<F>(bx * (long long)blockDim.x + threadIdx.x, nchains, pp.maxbins, pp.nbins, pp.prop_sd, pp.sd_stride,
+                         pp.dl, pp.prop, pp.logr, nullptr, seed_lo, seed_hi, itarg, chain0, pp.snap);
     else if (bx < pp.nbp + pp.nbu)
         mh_uniform_at((bx - pp.nbp) * (long long)blockDim.x + threadIdx.x, nchains, pp.nspec, pp.nbins, pp.nacc,
                       pp.n_iter_mh, seed_lo, seed_hi, itarg.get(), chain0, pp.u_out);
@@ -1440,7 +1491,8 @@ __global__ __launch_bounds__(256) void k_nc_prologue(int nblk_prop, int nblk_par
                                                      const int* __restrict__ ell2bin, const double* __restrict__ bl,
                                                      double k0, double k1, double k2, double* __restrict__ params,
                                                      const int* __restrict__ nbins_arr, const double* __restrict__ prop_sd,
-                                                     const double* __restrict__ dl, double* __restrict__ prop,
+                                                     int sd_stride, const double* __restrict__ dl,
+                                                     double* __restrict__ prop,
                                                      double* __restrict__ logr, const double* __restrict__ u_prop,
                                                      uint32_t seed_lo, uint32_t seed_hi, IterArg itarg, int chain0,
                                                      double* __restrict__ snap) {
@@ -1451,8 +1503,8 @@ __global__ __launch_bounds__(256) void k_nc_prologue(int nblk_prop, int nblk_par
         return;
     }
     if ((int)blockIdx.x < nblk_prop)
-        mh_propose_at<F>(blockIdx.x * (long long)blockDim.x + threadIdx.x, nchains, maxbins, nbins_arr, prop_sd, dl,
-                         prop, logr, u_prop, seed_lo, seed_hi, itarg, chain0, snap);
+        mh_propose_at<F>(blockIdx.x * (long long)blockDim.x + threadIdx.x, nchains, maxbins, nbins_arr, prop_sd, sd_stride,
+                         dl, prop, logr, u_prop, seed_lo, seed_hi, itarg, chain0, snap);
     else
         block_params_at<F, 1>(((int)blockIdx.x - nblk_prop) * blockDim.x + threadIdx.x, L, nchains, maxbins, dl,
                               ell2bin, bl, k0, k1, k2, params);
@@ -2503,6 +2555,12 @@ int gs_plan_create(const gs_model_desc* desc, gs_plan** out) {
         off += p->nblocks[sp] * p->n_iter_mh;
     }
     p->nacc = off;
+    p->nblk_mh = off / p->n_iter_mh;
+    p->bin2blk_h.assign((size_t)p->nspec * maxbins, -1);
+    for (int sp = 0; sp < p->nspec; ++sp)
+        for (int k = 0; k < p->nblocks[sp]; ++k)
+            for (int b = blocks[sp * (maxbins + 1) + k]; b < blocks[sp * (maxbins + 1) + k + 1]; ++b)
+                p->bin2blk_h[(size_t)sp * maxbins + b] = p->acc_off[sp] / p->n_iter_mh + k;
     // phases: F=1 [TT]; F=2 [EE, BB]; F=3 [EE, BB], [TT], [TE] (BB shares no
     // likelihood term with T/E; EE, TT, TE all enter the TE block)
     std::vector<std::vector<int>> phases;
@@ -2628,7 +2686,8 @@ int gs_plan_create(const gs_model_desc* desc, gs_plan** out) {
 int gs_plan_destroy(gs_plan* p) {
     if (!p) return 0;
     void* bufs[] = {p->iter_dev, p->ell2blk, p->gbuf, p->phase_tab, p->phase_rng, p->meta, p->bl, p->ell2bin, p->bins, p->blocks, p->prop_sd, p->tasks, p->partials, p->u_nat,
-                    p->params, p->stats, p->prop, p->logr, p->dl_tmp, p->cls_var, p->phase_tab_s, p->phase_rng_s, p->dmom};
+                    p->params, p->stats, p->prop, p->logr, p->dl_tmp, p->cls_var, p->phase_tab_s, p->phase_rng_s, p->dmom,
+                    p->bin2blk, p->mh_lam, p->mh_cnt, p->sd_chain};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     for (hipEvent_t e : p->ev) (void)hipEventDestroy(e);
@@ -2789,7 +2848,7 @@ static int stats_finish(gs_plan* p, double* stats, void* stream) {
 #define GS_FR(FF) hipLaunchKernelGGL((k_stats_finish_raw<FF>), dim3((unsigned)(nr + nbp + nbu)), dim3(256), 0,          \
                                      S(stream), p->L, p->nchains, p->ntile, p->nchunkg, tmf, p->partials, p->dmom,      \
                                      stats, op, nbp, nbu, p->u_nat, p->nspec, p->nacc, p->n_iter_mh, p->meta,           \
-                                     p->prop_sd, p->pro_dl, p->prop, p->logr, p->pro_slo, p->pro_shi,                   \
+                                     p->sd_tab(), p->sd_stride, p->pro_dl, p->prop, p->logr, p->pro_slo, p->pro_shi,    \
                                      p->ita(p->pro_it), p->chain0, p->dl_tmp)
         if (p->F == 1) GS_FR(1); else if (p->F == 2) GS_FR(2); else GS_FR(3);
 #undef GS_FR
@@ -2806,7 +2865,7 @@ static int stats_finish(gs_plan* p, double* stats, void* stream) {
 #define GS_FP(FF, GG) hipLaunchKernelGGL((k_stats_finish_pro<FF, GG>), dim3((unsigned)(n + nbp + nbu)), dim3(256), 0,   \
                                          S(stream), p->L, p->nchains, p->ntile, p->nchunkg, tmf, p->nstat, p->partials, \
                                          stats, nbp, nbu, p->u_nat, p->nspec, p->nacc, p->n_iter_mh, p->maxbins,        \
-                                         p->meta, p->prop_sd, p->pro_dl, p->prop, p->logr, p->pro_slo, p->pro_shi,      \
+                                         p->meta, p->sd_tab(), p->sd_stride, p->pro_dl, p->prop, p->logr, p->pro_slo, p->pro_shi, \
                                          p->ita(p->pro_it), p->chain0, p->dl_tmp)
 #define GS_FPG(FF) do { if (p->nchains <= 4) GS_FP(FF, 16); else GS_FP(FF, 4); } while (0)
         if (p->F == 1) GS_FPG(1); else if (p->F == 2) GS_FPG(2); else GS_FPG(3);
@@ -2893,7 +2952,7 @@ static int sweep_launch(gs_plan* p,const double* d_alm, const double* params, co
         pp.nbp = nblk((long long)p->nchains * p->nspec * p->maxbins, 256);
         pp.nbu = p->u_nat_ready ? nblk((long long)p->nchains * p->nacc, 256) : 0;
         pp.nspec = p->nspec; pp.nacc = p->nacc; pp.n_iter_mh = p->n_iter_mh; pp.maxbins = p->maxbins;
-        pp.nbins = p->meta; pp.prop_sd = p->prop_sd; pp.dl = p->pro_dl;
+        pp.nbins = p->meta; pp.prop_sd = p->sd_tab(); pp.sd_stride = p->sd_stride; pp.dl = p->pro_dl;
         pp.prop = p->prop; pp.logr = p->logr; pp.u_out = p->u_nat; pp.snap = p->dl_tmp;
     }
     pp.n = (pp.nbp + pp.nbu + pp.nbv + 7) / 8 * 8;
@@ -2964,7 +3023,7 @@ int gs_mh_propose(gs_plan* p, const double* dl, const double* u_prop, uint64_t s
     GS_CHECK(hipMemsetAsync(prop_out, 0, nprop * sizeof(double), S(stream)));
     GS_CHECK(hipMemsetAsync(logr_out, 0, nprop * sizeof(double), S(stream)));
 #define GS_MP(FF) hipLaunchKernelGGL((k_mh_propose<FF>), dim3(nblk(nprop, 256)), dim3(256), 0, S(stream), p->nchains, \
-                                     p->maxbins, p->meta, p->prop_sd, dl, prop_out, logr_out, u_prop, slo, shi,     \
+                                     p->maxbins, p->meta, p->sd_tab(), p->sd_stride, dl, prop_out, logr_out, u_prop, slo, shi, \
                                      p->ita(iteration), p->chain0, nullptr)
     if (p->F == 1) GS_MP(1); else if (p->F == 2) GS_MP(2); else GS_MP(3);
 #undef GS_MP
@@ -2987,13 +3046,93 @@ int gs_nc_mh(gs_plan* p, const double* stats, double* dl, const double* u_prop, 
     const uint32_t slo = (uint32_t)(seed & 0xFFFFFFFFu), shi = (uint32_t)(seed >> 32);
     const long long nprop = (long long)p->nchains * p->nspec * p->maxbins;
 #define GS_MP(FF) hipLaunchKernelGGL((k_mh_propose<FF>), dim3(nblk(nprop, 256)), dim3(256), 0, S(stream), p->nchains, \
-                                     p->maxbins, p->meta, p->prop_sd, dl, p->prop, p->logr, u_prop, slo, shi, p->ita(iteration), \
+                                     p->maxbins, p->meta, p->sd_tab(), p->sd_stride, dl, p->prop, p->logr, u_prop, slo, shi, p->ita(iteration), \
                                      p->chain0, p->dl_tmp)
     if (p->F == 1) GS_MP(1); else if (p->F == 2) GS_MP(2); else GS_MP(3);
 #undef GS_MP
     GS_LAUNCH_CHECK("k_mh_propose");
     p->snap_ok = true;
     return mh_decide(p, stats, dl, u_acc, slo, shi, iteration, accept_out, stream);
+}
+
+// ---- warm-up adaptation of the proposal scales ------------------------------
+static int sd_expand_launch(gs_plan* p, void* stream) {
+    const int nsb = p->nspec * p->maxbins;
+    hipLaunchKernelGGL(k_mh_sd_expand, dim3(nblk((long long)p->nchains * nsb, 256)), dim3(256), 0, S(stream),
+                       p->nchains, nsb, p->nblk_mh, p->bin2blk, p->prop_sd, p->mh_lam, p->sd_chain);
+    GS_LAUNCH_CHECK("k_mh_sd_expand");
+    return 0;
+}
+
+int gs_mh_adapt_enable(gs_plan* p, double target, double kappa) {
+    if (check_plan(p)) return -1;
+    if (!p->has_mh || p->nblk_mh < 1) return set_error("gs_mh_adapt_enable: plan has no MH blocks / proposal variances");
+    if (!(target > 0.0 && target < 1.0)) return set_error("gs_mh_adapt_enable: target must lie in (0, 1)");
+    if (!(kappa > 0.5 && kappa <= 1.0)) return set_error("gs_mh_adapt_enable: kappa must lie in (0.5, 1]");
+    p->adapt_target = target;
+    p->adapt_kappa = kappa;
+    if (p->adapt_on) return 0;               // the scales reached so far stay
+    const size_t nb = (size_t)p->nchains * p->nblk_mh;
+    int rc = 0;
+    if (!p->bin2blk) rc |= dev_upload(&p->bin2blk, p->bin2blk_h);
+    if (!p->mh_lam) rc |= dev_alloc(&p->mh_lam, nb);
+    if (!p->mh_cnt) rc |= dev_alloc(&p->mh_cnt, nb);
+    if (!p->sd_chain) rc |= dev_alloc(&p->sd_chain, (size_t)p->nchains * p->nspec * p->maxbins);
+    if (rc) return -1;
+    GS_CHECK(hipMemset(p->mh_lam, 0, nb * sizeof(double)));
+    GS_CHECK(hipMemset(p->mh_cnt, 0, nb * sizeof(int)));
+    if (sd_expand_launch(p, nullptr)) return -1;
+    GS_CHECK(hipDeviceSynchronize());
+    p->adapt_on = true;
+    p->sd_stride = p->nspec * p->maxbins;
+    return 0;
+}
+
+int gs_mh_adapt(gs_plan* p, const int32_t* accept, void* stream) {
+    if (check_plan(p)) return -1;
+    if (!p->adapt_on) return set_error("gs_mh_adapt: adaptation not enabled (gs_mh_adapt_enable)");
+    if (!accept) return set_error("gs_mh_adapt: null argument");
+    hipLaunchKernelGGL(k_mh_adapt_update, dim3(nblk((long long)p->nchains * p->nblk_mh, 256)), dim3(256), 0, S(stream),
+                       p->nchains, p->nblk_mh, p->n_iter_mh, accept, p->mh_lam, p->mh_cnt, p->adapt_target,
+                       p->adapt_kappa, p->adapt_lmax);
+    GS_LAUNCH_CHECK("k_mh_adapt_update");
+    return sd_expand_launch(p, stream);
+}
+
+int gs_mh_scale_get(gs_plan* p, double* log_scale, int32_t* count, void* stream) {
+    if (check_plan(p)) return -1;
+    if (!p->adapt_on) return set_error("gs_mh_scale_get: adaptation not enabled (gs_mh_adapt_enable)");
+    if (!log_scale && !count) return set_error("gs_mh_scale_get: null argument");
+    const size_t nb = (size_t)p->nchains * p->nblk_mh;
+    if (log_scale)
+        GS_CHECK(hipMemcpyAsync(log_scale, p->mh_lam, nb * sizeof(double), hipMemcpyDeviceToDevice, S(stream)));
+    if (count) GS_CHECK(hipMemcpyAsync(count, p->mh_cnt, nb * sizeof(int), hipMemcpyDeviceToDevice, S(stream)));
+    return 0;
+}
+
+int gs_mh_scale_set(gs_plan* p, const double* log_scale, const int32_t* count, void* stream) {
+    if (check_plan(p)) return -1;
+    if (!p->adapt_on) return set_error("gs_mh_scale_set: adaptation not enabled (gs_mh_adapt_enable)");
+    if (!log_scale) return set_error("gs_mh_scale_set: null argument");
+    const size_t nb = (size_t)p->nchains * p->nblk_mh;
+    GS_CHECK(hipMemcpyAsync(p->mh_lam, log_scale, nb * sizeof(double), hipMemcpyDeviceToDevice, S(stream)));
+    if (count) GS_CHECK(hipMemcpyAsync(p->mh_cnt, count, nb * sizeof(int), hipMemcpyDeviceToDevice, S(stream)));
+    return sd_expand_launch(p, stream);
+}
+
+int gs_mh_proposal_sd(gs_plan* p, double* sd_out, void* stream) {
+    if (check_plan(p)) return -1;
+    if (!sd_out) return set_error("gs_mh_proposal_sd: null argument");
+    if (!p->has_mh) return set_error("gs_mh_proposal_sd: plan has no MH blocks / proposal variances");
+    const size_t row = (size_t)p->nspec * p->maxbins * sizeof(double);
+    if (p->adapt_on) {
+        GS_CHECK(hipMemcpyAsync(sd_out, p->sd_chain, row * p->nchains, hipMemcpyDeviceToDevice, S(stream)));
+    } else {
+        for (int c = 0; c < p->nchains; ++c)
+            GS_CHECK(hipMemcpyAsync(reinterpret_cast<char*>(sd_out) + c * row, p->prop_sd, row,
+                                    hipMemcpyDeviceToDevice, S(stream)));
+    }
+    return 0;
 }
 
 // the MH phases proper (proposals already in p->prop / p->logr)
@@ -3119,7 +3258,8 @@ static int stats_to_nc_launch(gs_plan* p, const double* dl, double* stats, void*
         pp.nbp = nblk((long long)p->nchains * p->nspec * p->maxbins, 256);
         pp.n = pp.nbp;
         pp.nspec = p->nspec; pp.nacc = p->nacc; pp.n_iter_mh = p->n_iter_mh; pp.maxbins = p->maxbins;
-        pp.nbins = p->meta; pp.prop_sd = p->prop_sd; pp.dl = dl; pp.prop = p->prop; pp.logr = p->logr;
+        pp.nbins = p->meta; pp.prop_sd = p->sd_tab(); pp.sd_stride = p->sd_stride; pp.dl = dl; pp.prop = p->prop;
+        pp.logr = p->logr;
     }
     const uint32_t slo = (uint32_t)(seed & 0xFFFFFFFFu), shi = (uint32_t)(seed >> 32);
 #define GS_TN(FF) hipLaunchKernelGGL((k_stats_to_nc<FF>), dim3(nblk(n, 256) + (unsigned)pp.n), dim3(256), 0, S(stream), \
@@ -3212,7 +3352,7 @@ int gs_nc_prologue(gs_plan* p, const double* dl, const double* u_prop, uint64_t 
         }
 #define GS_PRQ(FF) hipLaunchKernelGGL((k_nc_prologue<FF>), dim3(nbq), dim3(256), 0, S(stream), 0, nbq, p->u_nat,     \
                                       p->nspec, p->nacc, p->n_iter_mh, p->L, p->nchains, p->maxbins, p->ell2bin, p->bl, \
-                                      p->kappa[0], p->kappa[1], p->kappa[2], p->params, p->meta, p->prop_sd, dl,        \
+                                      p->kappa[0], p->kappa[1], p->kappa[2], p->params, p->meta, p->sd_tab(), p->sd_stride, dl, \
                                       p->prop, p->logr, u_prop, slo, shi, p->ita(it), p->chain0, nullptr)
         if (p->F == 1) GS_PRQ(1); else if (p->F == 2) GS_PRQ(2); else GS_PRQ(3);
 #undef GS_PRQ
@@ -3224,7 +3364,7 @@ int gs_nc_prologue(gs_plan* p, const double* dl, const double* u_prop, uint64_t 
 #define GS_PRO(FF) hipLaunchKernelGGL((k_nc_prologue<FF>), dim3(nbp + nbq + nbu), dim3(256), 0, S(stream), nbp, nbq,   \
                                       p->u_nat, p->nspec, p->nacc, p->n_iter_mh, p->L,                                  \
                                       p->nchains, p->maxbins, p->ell2bin, p->bl, p->kappa[0], p->kappa[1], p->kappa[2], \
-                                      p->params, p->meta, p->prop_sd, dl, p->prop, p->logr, u_prop, slo, shi,            \
+                                      p->params, p->meta, p->sd_tab(), p->sd_stride, dl, p->prop, p->logr, u_prop, slo, shi, \
                                       p->ita(it), p->chain0, p->dl_tmp)
     if (p->F == 1) GS_PRO(1); else if (p->F == 2) GS_PRO(2); else GS_PRO(3);
 #undef GS_PRO

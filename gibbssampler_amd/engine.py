@@ -99,6 +99,7 @@ class GibbsPlan:
             a = np.array([np.sum(expo[b[i]:b[i + 1]]) - 1 for i in range(len(b) - 1)])
             a[0] = 1
             self._alphas[s] = a
+        self.adapting = False
         self._acc_layout = []
         if self.blocks is not None:
             for s in MH_ORDER[self.F]:
@@ -217,6 +218,55 @@ class GibbsPlan:
         C.check(self.lib.gs_nc_mh(self._h, C.ptr(stats), C.ptr(dl), C.ptr(u_prop), C.ptr(u_acc), int(seed),
                                   int(iteration), C.ptr(accept), self._s()), "gs_nc_mh")
         return accept
+
+    # ---- warm-up adaptation of the proposal scales (gs_mh_adapt_*) -------------------
+    @property
+    def nblocks_mh(self):
+        """MH blocks per chain, in the order of the accept flags."""
+        return self.nacc // self.n_iter_metropolis
+
+    def mh_block_layout(self):
+        """[(spectrum, first block, blocks)] of the [nchains, nblocks_mh] scale arrays."""
+        out, off = [], 0
+        for s, n in self._acc_layout:
+            out.append((s, off, n // self.n_iter_metropolis))
+            off += n // self.n_iter_metropolis
+        return out
+
+    def mh_adapt_enable(self, target=0.25, kappa=0.6):
+        """Per-chain proposal table and Robbins-Monro state (log-scale 0, count 0);
+        every proposal-drawing launch reads the per-chain table from here on."""
+        C.check(self.lib.gs_mh_adapt_enable(self._h, float(target), float(kappa)), "gs_mh_adapt_enable")
+        self.adapting = True
+
+    def mh_adapt(self, accept):
+        """One adaptation step from a step's accept flags [nchains, nacc] (capturable)."""
+        C.check(self.lib.gs_mh_adapt(self._h, C.ptr(accept), self._s()), "gs_mh_adapt")
+
+    def mh_scale_get(self):
+        """(log-scale fp64, count int32), device tensors [nchains, nblocks_mh]."""
+        lam = self.zeros(self.nchains, self.nblocks_mh)
+        cnt = self.zeros(self.nchains, self.nblocks_mh, dtype=torch.int32)
+        C.check(self.lib.gs_mh_scale_get(self._h, C.ptr(lam), C.ptr(cnt), self._s()), "gs_mh_scale_get")
+        return lam, cnt
+
+    def mh_scale_set(self, log_scale, count=None):
+        """Set the log-scales (and counts) and rebuild the per-chain table from them."""
+        lam = torch.as_tensor(log_scale, dtype=torch.float64).to(self.device).contiguous()
+        if tuple(lam.shape) != (self.nchains, self.nblocks_mh):
+            raise ValueError("log_scale must be [nchains, nblocks_mh]")
+        cnt = None
+        if count is not None:
+            cnt = torch.as_tensor(count).to(device=self.device, dtype=torch.int32).contiguous()
+            if tuple(cnt.shape) != (self.nchains, self.nblocks_mh):
+                raise ValueError("count must be [nchains, nblocks_mh]")
+        C.check(self.lib.gs_mh_scale_set(self._h, C.ptr(lam), C.ptr(cnt), self._s()), "gs_mh_scale_set")
+
+    def mh_proposal_sd(self):
+        """The proposal standard deviations the draws read, [nchains, nspec, maxbins]."""
+        sd = self.zeros(self.nchains, self.nspec, self.maxbins)
+        C.check(self.lib.gs_mh_proposal_sd(self._h, C.ptr(sd), self._s()), "gs_mh_proposal_sd")
+        return sd
 
     def stats_to_noncentered(self, dl, stats):
         C.check(self.lib.gs_stats_to_noncentered(self._h, C.ptr(dl), C.ptr(stats), self._s()), "gs_stats_to_nc")

@@ -220,6 +220,10 @@ class GibbsSampler:
         self.n_iter_metropolis = n_iter_metropolis
         self._runner = None
         self._tt = None
+        # warm-up adaptation of the NC Metropolis proposal scales (NonCenteredGibbs / ASIS)
+        self.n_warmup = 0
+        self.target_accept = 0.25
+        self._mean_accept_by_block = None
 
     # -- f4: temperature from pixel data (reference semantics, gibbssampler_amd.tt) -----------
     def _tt_pixel_path(self, all_sph):
@@ -313,8 +317,17 @@ class GibbsSampler:
         runner = self._make_runner()
         resume, self._resume_state = getattr(self, "_resume_state", None), None
         init = dls_init if isinstance(dls_init, dict) or resume is not None else {self.spectra[0]: dls_init}
+        kw = {"n_warmup": self.n_warmup, "target_accept": self.target_accept} if self.n_warmup else {}
+        first = runner.iteration if resume is None else int(resume["iteration"])
         h, acc, t = runner.run(init, self.n_iter, timings=True,
-                               gather=self.shard.gather if self.shard is not None else None, resume=resume)
+                               gather=self.shard.gather if self.shard is not None else None, resume=resume, **kw)
+        if acc is not None:
+            # acceptance per MH block over the frozen (post warm-up) steps and all chains
+            k0 = min(max(runner.n_warmup - (0 if resume is None else first), 0), self.n_iter)
+            nm = self.n_iter_metropolis
+            self._mean_accept_by_block = {
+                s: (v[k0:].reshape(-1, v.shape[2] // nm, nm).mean(axis=(0, 2)) if v.shape[0] > k0 else
+                    np.full(v.shape[2] // nm, np.nan)) for s, v in acc.items()}
         h = {s: self._squeeze(v) for s, v in h.items()}
         if acc is not None:
             acc = {s: self._squeeze(v) for s, v in acc.items()}
@@ -349,6 +362,31 @@ class GibbsSampler:
 
     def run_temperature(self, dls_init):
         raise NotImplementedError
+
+    # -- warm-up adaptation (NonCenteredGibbs / ASIS, full sky) ------------------------------
+    def _set_warmup(self, n_warmup, target_accept):
+        from .samplers import check_warmup
+        self.n_warmup = check_warmup(self._kind, self.rng, n_warmup, target_accept)
+        self.target_accept = float(target_accept)
+        if self.n_warmup > 0 and (self.mask is not None or getattr(self, "tt_pixel", False)):
+            raise NotImplementedError("n_warmup > 0: masked and TT-pixel runs use the pixel-domain Metropolis step "
+                                      "(one shared proposal table); the warm-up adaptation covers the full-sky "
+                                      "harmonic (all_sph) samplers only")
+
+    @property
+    def tuned_proposal_variances(self):
+        """After a run with n_warmup > 0: per spectrum the [nbins-2] proposal
+        variances at the adapted scales (geometric mean over all chains), ready
+        to be passed as proposal_variances= to a production run."""
+        if self._runner is None:
+            raise RuntimeError("tuned_proposal_variances: nothing has run yet")
+        return self._runner.tuned_proposal_variances(self.shard.gather if self.shard is not None else None)
+
+    @property
+    def mean_accept_by_block(self):
+        """Per spectrum the acceptance rate of every MH block over the frozen
+        (post warm-up) iterations of the last run, pooled over chains."""
+        return self._mean_accept_by_block
 
     @property
     def skymap(self):
@@ -429,12 +467,13 @@ class NonCenteredGibbs(GibbsSampler):
 
     def __init__(self, pix_map, noise_I, noise_Q, beam, nside, lmax, Npix, proposal_variances,
                  metropolis_blocks=None, polarization=False, bins=None, n_iter=10000, n_iter_metropolis=1,
-                 mask_path=None, all_sph=False, **kw):
+                 mask_path=None, all_sph=False, n_warmup=0, target_accept=0.25, **kw):
         super().__init__(pix_map, noise_I, beam, nside, lmax, polarization=polarization, bins=bins, n_iter=n_iter,
                          mask_path=mask_path, noise_pol=noise_Q, proposal_variances=proposal_variances,
                          metropolis_blocks=metropolis_blocks, n_iter_metropolis=n_iter_metropolis, **kw)
         self.all_sph = all_sph
         self.tt_pixel = self._tt_pixel_path(all_sph)
+        self._set_warmup(n_warmup, target_accept)
         if self.tt_pixel:
             from .tt import TTNonCenteredConstrainedRealization, TTNonCenteredClsSampler
             m = self._tt_model(True)
@@ -473,7 +512,8 @@ class ASIS(GibbsSampler):
 
     def __init__(self, pix_map, noise, noise_Q, beam, nside, lmax, Npix, proposal_variances, metropolis_blocks=None,
                  polarization=False, bins=None, n_iter=10000, n_iter_metropolis=1, mask_path=None, gibbs_cr=False,
-                 rj_step=False, all_sph=False, n_gibbs=20, overrelaxation=False, **kw):
+                 rj_step=False, all_sph=False, n_gibbs=20, overrelaxation=False, n_warmup=0, target_accept=0.25,
+                 **kw):
         super().__init__(pix_map, noise, beam, nside, lmax, polarization=polarization, bins=bins, n_iter=n_iter,
                          gibbs_cr=gibbs_cr, rj_step=rj_step, mask_path=mask_path, noise_pol=noise_Q,
                          proposal_variances=proposal_variances, metropolis_blocks=metropolis_blocks,
@@ -482,6 +522,7 @@ class ASIS(GibbsSampler):
         self.n_gibbs = n_gibbs
         self.overrelaxation = overrelaxation
         self.tt_pixel = self._tt_pixel_path(all_sph)
+        self._set_warmup(n_warmup, target_accept)
         if self.tt_pixel:
             from .tt import TTCenteredConstrainedRealization, TTCenteredClsSampler, TTNonCenteredClsSampler
             m = self._tt_model(True)

@@ -333,10 +333,13 @@ def write_map(filename, m, nest=False, dtype=np.float32, column_names=None, over
 # ---------------------------------------------------------------------------------------
 def run_record(h_cls, h_accept_cr, h_duration_cr, bins, blocks, proposal_variances, total_time, total_cpu_time,
                pcg_accuracy=None, rj_step=False, gibbs_iterations=None, gibbs_cr=False, h_accept_nc=None,
-               h_duration_cls_centered=None, h_duration_cls_non_centered=None, h_duration_iteration=None):
+               h_duration_cls_centered=None, h_duration_cls_non_centered=None, h_duration_iteration=None,
+               tuned_proposal_variances=None, n_warmup=None):
     """the dict main_polarization.py:172-181 builds (same keys; the reference
-    stores h_accept_cr under both h_accept_nc and h_accept_cr)."""
-    return {"h_cls": h_cls, "h_accept_nc": h_accept_cr if h_accept_nc is None else h_accept_nc,
+    stores h_accept_cr under both h_accept_nc and h_accept_cr).  A run that
+    adapted its proposal scales (n_warmup > 0) also stores the tuned variances
+    next to the given ones: tuned_proposal_variances_<spectrum>, n_warmup."""
+    rec = {"h_cls": h_cls, "h_accept_nc": h_accept_cr if h_accept_nc is None else h_accept_nc,
             "h_duration_cls_centered": h_duration_cls_centered, "h_duration_cr": h_duration_cr,
             "bins_EE": bins["EE"], "bins_BB": bins["BB"], "blocks_EE": blocks["EE"],
             "h_duration_cls_non_centered": h_duration_cls_non_centered,
@@ -345,6 +348,11 @@ def run_record(h_cls, h_accept_cr, h_duration_cr, bins, blocks, proposal_varianc
             "total_cpu_time": total_cpu_time, "pcg_accuracy": pcg_accuracy, "h_accept_cr": h_accept_cr,
             "total_time": total_time, "rj_step": rj_step, "gibbs_iterations": gibbs_iterations,
             "gibbs_cr": gibbs_cr}
+    if tuned_proposal_variances is not None:
+        for s, v in tuned_proposal_variances.items():
+            rec["tuned_proposal_variances_" + s] = np.asarray(v, dtype=np.float64)
+        rec["n_warmup"] = 0 if n_warmup is None else int(n_warmup)
+    return rec
 
 
 def dataset_record(pix_map, skymap_true, cls_, fwhm_beam, noise_var_temp, noise_var_pol, mask_path, nside, lmax,

@@ -27,6 +27,49 @@ from . import _capi as C
 from .engine import GibbsPlan, MH_ORDER
 
 INIT_ITER = 0xFFFFFFFF
+ADAPT_KAPPA = 0.6       # Robbins-Monro step n^-kappa of the warm-up adaptation
+
+
+def check_warmup(kind, rng, n_warmup, target_accept=0.25):
+    """Argument check of run(n_warmup=...): the warm-up adapts the NC Metropolis
+    proposal scales, which only the native NC / ASIS samplers have."""
+    n_warmup = int(n_warmup)
+    if n_warmup < 0:
+        raise ValueError("n_warmup must be >= 0")
+    if n_warmup > 0:
+        if kind == "centered":
+            raise ValueError("n_warmup > 0: the centered sampler has no Metropolis step to adapt")
+        if rng != "native":
+            raise ValueError("n_warmup > 0 needs rng='native' (a replayed run reproduces the reference's "
+                             "fixed proposal scales)")
+        if not 0.0 < float(target_accept) < 1.0:
+            raise ValueError("target_accept must lie in (0, 1)")
+    return n_warmup
+
+
+def warmup_of_state(st):
+    """(n_warmup, target_accept, log_scale, count) of a state_dict(); states
+    written before the adaptation existed (no such keys) are 'not adapting'."""
+    if st.get("mh_log_scale") is None:
+        return 0, 0.25, None, None
+    return int(st.get("mh_n_warmup", 0)), float(st.get("mh_target_accept", 0.25)), st["mh_log_scale"], \
+        st.get("mh_count")
+
+
+def tuned_variances(proposal_variances, blocks, bins, layout, log_scale_mean):
+    """sd0^2 exp(2 lam) per spectrum and bin >= 2 (the form proposal_variances=
+    takes): layout [(spectrum, first block, blocks)] of log_scale_mean."""
+    out = {}
+    for s, off, nb in layout:
+        pv = np.array(proposal_variances[s], dtype=np.float64)
+        nbins = len(bins[s]) - 1
+        edges = np.clip(np.asarray(blocks[s], dtype=np.int64), 0, nbins)
+        for k in range(nb):
+            lo, hi = max(int(edges[k]), 2), int(edges[k + 1])
+            if hi > lo:
+                pv[lo - 2:hi - 2] *= np.exp(2.0 * float(log_scale_mean[off + k]))
+        out[s] = pv
+    return out
 
 
 @contextlib.contextmanager
@@ -75,6 +118,10 @@ class BatchedRunner:
         self.materialize_recentre = materialize_recentre
         self.iteration = 0
         self.graph = None
+        # warm-up adaptation of the MH proposal scales: iterations 1 .. n_warmup adapt
+        self.n_warmup = 0
+        self.target_accept = 0.25
+        self._gather = None
 
     def __del__(self):
         # dropped inside another sampler's capture: keep the kept hipGraphs, the
@@ -130,6 +177,11 @@ class BatchedRunner:
               "chain0": p.chain0, "nchains": p.nchains, "lmax": p.L, "nfields": p.F,
               "dl": self.dl.cpu().clone(), "dl_tmp": self.dl_tmp.cpu().clone(), "accept": self.accept.cpu().clone(),
               "s": None if self.s is None else self.s.cpu().clone()}
+        if p.adapting:
+            # the proposal log-scales, their step counts and where the warm-up ends
+            lam, cnt = p.mh_scale_get()
+            st.update(mh_log_scale=lam.cpu(), mh_count=cnt.cpu(), mh_n_warmup=int(self.n_warmup),
+                      mh_target_accept=float(self.target_accept))
         if self.rng == "replay":
             name, keys, pos, has_gauss, cached = np.random.get_state()
             st.update(numpy_rng_keys=torch.from_numpy(np.asarray(keys, dtype=np.int64)), numpy_rng_pos=int(pos),
@@ -162,6 +214,13 @@ class BatchedRunner:
         self.iteration = int(st["iteration"])
         self.graph = None
         p.iteration_counter(False)
+        nw, target, lam, cnt = warmup_of_state(st)
+        if lam is not None:
+            self._adapt_enable(target)
+            p.mh_scale_set(lam, cnt)
+        # a state without scales (older checkpoints) is "not adapting": no warm-up
+        # is left, and the plan's proposal table stays as it is
+        self.n_warmup = nw
         if self.rng == "replay" and "numpy_rng_keys" in st:
             np.random.set_state(("MT19937", st["numpy_rng_keys"].numpy().astype(np.uint32), st["numpy_rng_pos"],
                                  st["numpy_rng_has_gauss"], st["numpy_rng_cached"]))
@@ -197,8 +256,35 @@ class BatchedRunner:
         self.graph_steps = 1
         return g
 
+    def _adapt_enable(self, target):
+        """Per-chain proposal table on (or a new target): graphs captured before
+        hold the old table / target as kernel arguments and are dropped."""
+        p = self.plan
+        if p.adapting and float(target) == self.target_accept:
+            return
+        p.mh_adapt_enable(target, ADAPT_KAPPA)
+        self.target_accept = float(target)
+        self.__dict__.pop("_run_graphs", None)
+        self.graph = None
+
+    def tuned_proposal_variances(self, gather=None):
+        """Per spectrum the [nbins-2] variances sd0^2 exp(2 mean_chains(log-scale)),
+        i.e. the geometric mean of the chains' scales, in the form
+        ``proposal_variances=`` accepts (a preliminary run's output for the
+        production run).  gather: ShardContext.gather -- the mean is over every
+        rank's chains (default: the gather of the last run())."""
+        p = self.plan
+        if not p.adapting:
+            return {s: np.array(v, dtype=np.float64) for s, v in p.proposal_variances.items()}
+        lam, _ = p.mh_scale_get()
+        gather = gather if gather is not None else self._gather
+        if gather is not None:
+            lam = gather(lam, dim=0)
+        return tuned_variances(p.proposal_variances, p.blocks, p.bins, p.mh_block_layout(),
+                               lam.mean(dim=0).cpu().numpy())
+
     def capture_steps(self, nsteps, trace=None, trace_capacity=None, time_sweeps=False, time_every=1,
-                      accept_trace=None):
+                      accept_trace=None, adapt=False):
         """Native RNG: capture ``nsteps`` whole iterations in ONE hipGraph (one
         replay = nsteps steps).  time_sweeps: bracket the CR-sweep kernel of every
         ``time_every``-th step by event-record nodes (plan.sweep_timing), so the
@@ -235,6 +321,11 @@ class BatchedRunner:
                         p.step_asis_fused(self.d, self.dl, self.s, seed=self.seed, accept=acc,
                                           dl_tmp=self.dl_tmp, recentre=self.materialize_recentre, trace=trace,
                                           capacity=trace_capacity or 0)
+                    if adapt:
+                        # after this step's decisions, before the next launch that
+                        # draws proposals (prologue, sweep / finish front, ASIS's
+                        # statistics launch): all later on this stream
+                        p.mh_adapt(acc)
         finally:
             # back to one step per replay even when a launch raised inside the capture
             p.graph_step(0, 1)
@@ -267,18 +358,38 @@ class BatchedRunner:
         self.iteration = it
 
     # -- a whole run --------------------------------------------------------------------
-    def run(self, dls_init, n_iter, timings=False, gather=None, graph_chunk=32, resume=None):
+    def run(self, dls_init, n_iter, timings=False, gather=None, graph_chunk=32, resume=None, n_warmup=0,
+            target_accept=0.25):
         """n_iter iterations from dls_init; returns (histories, accepts[, step
         times]).  gather: ShardContext.gather of a torchrun job -- the device
         histories of every rank are all-gathered along the chain axis (global
         chain order) before the one copy to the host.  resume: a state_dict()
         to continue from instead of starting at dls_init (the history's first
-        row is then the restored D_l, i.e. the previous run's last row)."""
+        row is then the restored D_l, i.e. the previous run's last row).
+        n_warmup: the first n_warmup iterations adapt the MH proposal scale of
+        every (chain, block) towards the acceptance rate target_accept
+        (Robbins-Monro on the log-scale, on the device); the scales are frozen
+        for the rest, an ordinary MH chain.  The histories keep their shape
+        (warm-up rows included); runner.n_warmup is the iteration the warm-up
+        ends at.  A resumed state carries its own warm-up bookkeeping and goes
+        on with it; n_warmup > 0 with a resume adds that many warm-up iterations."""
         p = self.plan
+        n_warmup = check_warmup(self.kind, self.rng, n_warmup, target_accept)
+        self._gather = gather
         if resume is not None:
             self.load_state_dict(resume)
+            if n_warmup > 0:
+                self._adapt_enable(target_accept)
+                self.n_warmup = self.iteration + n_warmup
         else:
             self.init(dls_init)
+            self.n_warmup = n_warmup
+            if n_warmup > 0:
+                self._adapt_enable(target_accept)
+                p.mh_scale_set(torch.zeros(p.nchains, p.nblocks_mh, dtype=torch.float64),
+                               torch.zeros(p.nchains, p.nblocks_mh, dtype=torch.int32))
+        # steps of this run that adapt; warm-up and frozen steps never share a graph
+        n_adapt = min(max(self.n_warmup - self.iteration, 0), n_iter)
         with_start = self.kind != "asis"
         H = p.zeros(n_iter + (1 if with_start else 0), p.nchains, p.nspec, p.maxbins)
         A = p.zeros(n_iter, p.nchains, max(p.nacc, 1), dtype=torch.int32)
@@ -311,16 +422,19 @@ class BatchedRunner:
             p.iteration_counter(True, self.iteration + 1)
             done = 0
             while done < n_iter:
-                k = min(chunk, n_iter - done)
-                if k not in cache:
-                    cache[k] = self.capture_steps(k, trace=trace, trace_capacity=chunk, accept_trace=acc_tr)
+                adapt = done < n_adapt
+                k = min(chunk, (n_adapt if adapt else n_iter) - done)
+                key = ("adapt", k) if adapt else k
+                if key not in cache:
+                    cache[key] = self.capture_steps(k, trace=trace, trace_capacity=chunk, accept_trace=acc_tr,
+                                                    adapt=adapt)
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 # the trace record of iteration it goes to slot (it - 1) % chunk: a
                 # run resumed at an iteration that is not a multiple of chunk starts
                 # mid-ring
                 r0 = self.iteration % chunk
                 e0.record()
-                cache[k].replay()
+                cache[key].replay()
                 self.iteration += k
                 e1.record()
                 h0, h1 = (0 if done == 0 else off + done), off + done + k
@@ -352,6 +466,8 @@ class BatchedRunner:
         for i in range(n_iter):
             t0 = time.perf_counter() if timings else 0.0
             self.step()
+            if i < n_adapt:
+                p.mh_adapt(self.accept)
             H[i + (1 if with_start else 0)].copy_(self.dl)
             if self.kind != "centered":
                 A[i].copy_(self.accept)

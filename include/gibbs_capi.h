@@ -148,6 +148,32 @@ int gs_mh_propose(gs_plan* plan, const double* dl, const double* u_prop, uint64_
 int gs_nc_mh(gs_plan* plan, const double* stats, double* dl_binned,
              const double* u_prop_replay, const double* u_accept_replay,
              uint64_t seed, uint32_t iteration, int32_t* accept_out, void* stream);
+/* Warm-up adaptation of the NC Metropolis proposal scales (Robbins-Monro, per
+ * chain and MH block).  State: a log-scale lam and a step count n, both
+ * [nchains][nblocks] with nblocks = nblocks_total / n_iter_metropolis and block
+ * j in the order of the accept flags (flags j * n_iter_metropolis ... of a
+ * chain belong to block j).  gs_mh_adapt, after the decisions of one step:
+ *   abar = mean of the block's accept flags,  n <- n + 1,
+ *   lam <- clamp(lam + n^-kappa (abar - target), -20, 20),
+ *   sd[chain][spectrum][bin] = sd0[spectrum][bin] exp(lam[chain][block of bin])
+ * with sd0 the sqrt of the plan's proposal variances.
+ * gs_mh_adapt_enable allocates the state (lam = 0, n = 0) and the per-chain
+ * table and makes every proposal-drawing launch of the plan read that table
+ * (at lam = 0 it holds sd0: the same proposals, bit for bit); a second call
+ * only changes target / kappa.  It synchronises the device: call it outside
+ * a capture.  A plan without MH blocks or proposal variances is an error.
+ * gs_mh_adapt is two small launches on the stream (capturable, no host
+ * synchronisation): call it after the step's decide launch and before the
+ * next launch that draws proposals.  Not calling it freezes the scales.
+ * gs_mh_scale_get / _set copy lam (and n, nullable) from / to DEVICE buffers;
+ * set rebuilds the table by the code gs_mh_adapt uses, so restored scales give
+ * the same table bit for bit.  gs_mh_proposal_sd copies the table the
+ * proposals read to sd_out [nchains][nspec][maxbins] (adaptation on or off). */
+int gs_mh_adapt_enable(gs_plan* plan, double target, double kappa);
+int gs_mh_adapt(gs_plan* plan, const int32_t* accept, void* stream);
+int gs_mh_scale_get(gs_plan* plan, double* log_scale, int32_t* count, void* stream);
+int gs_mh_scale_set(gs_plan* plan, const double* log_scale, const int32_t* count, void* stream);
+int gs_mh_proposal_sd(gs_plan* plan, double* sd_out, void* stream);
 /* stats of s_nc = A(C)^+ s with A = chol(C(dl_binned)) (ASIS non-centering) */
 int gs_stats_to_noncentered(gs_plan* plan, const double* dl_binned, double* stats, void* stream);
 /* s <- T_l s for T_l = A(C(dl_new)) [A(C(dl_old))^+ unless dl_old NULL] */
