@@ -20,7 +20,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SOURCES = [os.path.join(HERE, "csrc", "gs_kernels.hip"), os.path.join(HERE, "csrc", "gs_sht.hip"),
            os.path.join(HERE, "csrc", "gs_masked.hip")]
-HEADERS = [os.path.join(HERE, "csrc", h) for h in ("gs_rng.h", "gs_common.h", "gs_bm_tables.h", "gs_block.h")] + \
+HEADERS = [os.path.join(HERE, "csrc", h) for h in ("gs_rng.h", "gs_common.h", "gs_bm_tables.h", "gs_block.h",
+                                                         "gs_launch.h")] + \
     [os.path.join(ROOT, "include", "gibbs_capi.h")]
 LIB = os.path.join(HERE, "libgibbs_hip.so")
 ARCH = os.environ.get("GIBBS_OFFLOAD_ARCH", "gfx950")

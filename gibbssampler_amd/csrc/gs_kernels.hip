@@ -28,12 +28,17 @@
 #include "gs_rng.h"
 #include "gs_common.h"
 #include "gs_block.h"
+#include "gs_launch.h"
 
 using namespace gs;
 
 namespace {
 
 using gs_detail::set_error;
+using gs_detail::with_F;
+using gs_detail::SeedWords;
+using gs_detail::seed_words;
+using gs_detail::nblk;
 
 constexpr int WAVE = 64;
 constexpr int NP = GS_NPARAM;
@@ -117,19 +122,12 @@ struct gs_plan {
     bool raw_on = true;
     double* dmom = nullptr;          // [ND][L+1] data moments
     const double* dmom_src = nullptr;    // the data tensor they belong to
-    bool raw_pending = false;        // the partials hold raw sums (of a sweep at raw_dl)
-    const double* raw_dl = nullptr;
-    // many-chain native NC steps: the prologue's parameter table is launched by
-    // gs_nc_sweep only when its sweep needs it (replayed normals, stored map)
-    bool par_pending = false;
-    const double* par_dl = nullptr;
     double* params = nullptr;        // [nchains][L+1][NP]
     double* stats = nullptr;         // [nchains][nstat][L+1]
     double* prop = nullptr;          // [nchains][nspec][maxbins]
     double* logr = nullptr;          // [nchains][nspec][maxbins]
     double* dl_tmp = nullptr;        // [nchains][nspec][maxbins]
     double* u_nat = nullptr;         // [nchains][nacc] native MH accept uniforms drawn by the prologue
-    bool u_nat_ready = false;
     // device iteration counter (hipGraph replay of whole steps)
     uint32_t* iter_dev = nullptr;
     // few-chain centered steps: the C_l draw's random variates (Gamma / normal)
@@ -141,18 +139,44 @@ struct gs_plan {
     bool cls_pre = false;
     bool cls_pre_many = false;       // the same for many chains: front workgroups of the throughput sweep
     double* cls_var = nullptr;       // [nchains][nspec][maxbins][3]
-    // many-chain NC steps: the MH proposals and native accept uniforms depend
-    // only on the current D_l and the counters, so they are drawn by extra
-    // workgroups at the front of the CR sweep's launch (or, when the sweep
-    // cannot take them -- replayed normals -- of the statistics finish) instead
-    // of in the prologue, which keeps the block parameters alone
-    bool pro_pending = false;        // a prologue deferred its draws to the sweep / finish
-    // the proposal launch of this step also wrote a snapshot of the chains'
-    // D_l into dl_tmp: the split MH reads its start state from there (both
-    // workgroups of a chain see the pre-MH D_l whatever their order)
-    bool snap_ok = false;
-    const double* pro_dl = nullptr;
-    uint32_t pro_slo = 0, pro_shi = 0, pro_it = 0;
+    // Work that one call of a step leaves to a later call of the same step:
+    //
+    //   member       set by                                consumed by
+    //   pro_pending  gs_nc_prologue, native draws with a   sweep_launch (throughput form, native,
+    //   (pro_dl,     parameter table or > 4 chains         not given, iteration == pro_it), else
+    //   pro_seed,    (cleared when it launches the         stats_finish; gs_nc_decide[_fused]
+    //   pro_it)      draws itself)                         refuse to run while it is set
+    //   u_nat_ready  gs_nc_prologue, every call            read, never cleared: the front
+    //                                                      workgroups' uniforms, gs_nc_decide_fused
+    //   snap_ok      whichever launch made the proposals   mh_decide, every call (cleared there);
+    //                with a D_l snapshot (prologue, sweep  gs_nc_prologue clears it first
+    //                front, statistics finish, gs_nc_mh)
+    //   par_pending  gs_nc_prologue, when raw_on defers    gs_nc_sweep (launches the table only if
+    //   (par_dl)     the parameter table                   its sweep reads one)
+    //   raw_pending  sweep_launch, every call (= raw)      stats_finish; gs_nc_stats refuses to
+    //   (raw_dl)                                           run while it is set
+    struct Deferred {
+        // many-chain NC steps: the MH proposals and native accept uniforms depend
+        // only on the current D_l and the counters, so they are drawn by extra
+        // workgroups at the front of the CR sweep's launch (or, when the sweep
+        // cannot take them -- replayed normals -- of the statistics finish) instead
+        // of in the prologue, which keeps the block parameters alone
+        bool pro_pending = false;
+        const double* pro_dl = nullptr;
+        gs_detail::SeedWords pro_seed{0, 0};
+        uint32_t pro_it = 0;
+        bool u_nat_ready = false;    // the step's accept uniforms are the native ones (u_nat)
+        // the proposal launch of this step also wrote a snapshot of the chains'
+        // D_l into dl_tmp: the split MH reads its start state from there (both
+        // workgroups of a chain see the pre-MH D_l whatever their order)
+        bool snap_ok = false;
+        // many-chain native NC steps: the prologue's parameter table is launched by
+        // gs_nc_sweep only when its sweep needs it (replayed normals, stored map)
+        bool par_pending = false;
+        const double* par_dl = nullptr;
+        bool raw_pending = false;    // the partials hold raw sums (of a sweep at raw_dl)
+        const double* raw_dl = nullptr;
+    } defer;
     bool iter_dev_on = false;
     const uint32_t* itp() const { return iter_dev_on ? iter_dev : nullptr; }
     // graph-captured steps (gs_graph_step): this step's offset from the device
@@ -2389,7 +2413,6 @@ int dev_alloc(T** dst, size_t n) {
 }
 
 inline hipStream_t S(void* s) { return (hipStream_t)s; }
-inline unsigned nblk(long long n, int bs) { return (unsigned)std::max<long long>(1, std::min<long long>((n + bs - 1) / bs, 1 << 20)); }
 
 void build_tasks(gs_plan* p) {
     const int L = p->L;
@@ -2470,6 +2493,29 @@ void build_tasks(gs_plan* p) {
 int check_plan(const gs_plan* p) {
     if (!p) return set_error("null plan");
     return 0;
+}
+
+// the finish kernels' chunk loads in flight: G = 16 for few chains, 4 for many (stats_finish_sum)
+template <typename Fn>
+void with_G(const gs_plan* p, Fn&& fn) {
+    if (p->nchains <= 4) fn(std::integral_constant<int, 16>{});
+    else fn(std::integral_constant<int, 4>{});
+}
+
+using SweepKernel = void (*)(int, int, int, int, int, int, const int2*, const double*, const double*, const double*,
+                             double*, double*, uint32_t, uint32_t, IterArg, uint32_t, int, SweepOp, ClsPre, ProPre, int);
+
+// every k_cr_sweep<F, ZM, STORE, PRE, RAW> the library launches: the latency
+// form (PRE = 4: native draws, raw or not), the given map (ZM = 2), replayed
+// normals (ZM = 1), native raw and native plain; st: the map is stored
+template <int F>
+SweepKernel sweep_variant(bool lat, bool given, bool rep, bool raw, bool st) {
+    if (lat && raw) return st ? k_cr_sweep<F, 0, true, 4, true> : k_cr_sweep<F, 0, false, 4, true>;
+    if (lat) return st ? k_cr_sweep<F, 0, true, 4> : k_cr_sweep<F, 0, false, 4>;
+    if (given) return k_cr_sweep<F, 2, false>;
+    if (rep) return st ? k_cr_sweep<F, 1, true> : k_cr_sweep<F, 1, false>;
+    if (raw) return st ? k_cr_sweep<F, 0, true, 0, true> : k_cr_sweep<F, 0, false, 0, true>;
+    return st ? k_cr_sweep<F, 0, true> : k_cr_sweep<F, 0, false>;
 }
 
 }  // namespace
@@ -2777,18 +2823,14 @@ int gs_unfold_bins(int n, const double* binned, const int* bins, int nbins, doub
 int gs_block_params(gs_plan* p, int mode, const double* dl, double* params, void* stream) {
     if (check_plan(p)) return -1;
     if (!dl || !params) return set_error("gs_block_params: null argument");
+    if (mode != GS_MODE_CENTERED && mode != GS_MODE_NONCENTERED) return set_error("gs_block_params: bad mode");
     const long long n = (long long)p->nchains * (p->L + 1);
-    const dim3 g(nblk(n, 256)), b(256);
-#define GS_BP(FF, MM) hipLaunchKernelGGL((k_block_params<FF, MM>), g, b, 0, S(stream), p->L, p->nchains, p->maxbins, dl, \
-                                         p->ell2bin, p->bl, p->kappa[0], p->kappa[1], p->kappa[2], params)
-    if (mode == GS_MODE_CENTERED) {
-        if (p->F == 1) GS_BP(1, 0); else if (p->F == 2) GS_BP(2, 0); else GS_BP(3, 0);
-    } else if (mode == GS_MODE_NONCENTERED) {
-        if (p->F == 1) GS_BP(1, 1); else if (p->F == 2) GS_BP(2, 1); else GS_BP(3, 1);
-    } else {
-        return set_error("gs_block_params: bad mode");
-    }
-#undef GS_BP
+    with_F(p->F, [&](auto f) {
+        constexpr int F = decltype(f)::value;
+        const auto k = mode == GS_MODE_CENTERED ? k_block_params<F, 0> : k_block_params<F, 1>;
+        hipLaunchKernelGGL(k, dim3(nblk(n, 256)), dim3(256), 0, S(stream), p->L, p->nchains, p->maxbins, dl, p->ell2bin,
+                           p->bl, p->kappa[0], p->kappa[1], p->kappa[2], params);
+    });
     GS_LAUNCH_CHECK("k_block_params");
     return 0;
 }
@@ -2831,161 +2873,174 @@ static int timing_begin(gs_plan* p, hipStream_t s, hipEvent_t* e0, hipEvent_t* e
     return record_ev(*e0, s);
 }
 
+// ---- extra workgroups of the sweep / statistics finish / prologue launches ----
+// the workgroups that draw the MH proposals from dl (uniforms: and the native
+// accept uniforms; snapshot: the proposals also copy dl to dl_tmp for the split
+// MH).  n, the launch's count of front workgroups, is the caller's to set.
+static ProPre pro_front(const gs_plan* p, const double* dl, bool snapshot, bool uniforms) {
+    ProPre pp{};
+    pp.nbp = nblk((long long)p->nchains * p->nspec * p->maxbins, 256);
+    pp.nbu = uniforms ? nblk((long long)p->nchains * p->nacc, 256) : 0;
+    pp.nspec = p->nspec; pp.nacc = p->nacc; pp.n_iter_mh = p->n_iter_mh; pp.maxbins = p->maxbins;
+    pp.nbins = p->meta; pp.prop_sd = p->sd_tab(); pp.sd_stride = p->sd_stride; pp.dl = dl;
+    pp.prop = p->prop; pp.logr = p->logr; pp.u_out = p->u_nat; pp.snap = snapshot ? p->dl_tmp : nullptr;
+    return pp;
+}
+
+// the workgroups that draw the C_l draw's variates into cls_var
+static ClsPre cls_front(const gs_plan* p) {
+    ClsPre cp{};
+    cp.nspec = p->nspec; cp.maxbins = p->maxbins; cp.bins = p->bins; cp.nbins = p->meta; cp.out = p->cls_var;
+    cp.nitem = p->nchains * p->nspec * p->maxbins;
+    cp.n = (cp.nitem + 255) / 256;
+    return cp;
+}
+
+// the prologue's deferred draws (seed and iteration: defer.pro_seed, defer.pro_it),
+// pending no longer; none pending: no workgroups
+static ProPre take_pro(gs_plan* p) {
+    if (!p->defer.pro_pending) return ProPre{};
+    p->defer.pro_pending = false;
+    return pro_front(p, p->defer.pro_dl, true, p->defer.u_nat_ready);
+}
+
+// rows behind one statistics partial (a sweep workgroup adds its chunks of a tile)
+static int finish_tm(const gs_plan* p) { return p->rows_per_task * (4 / p->sweep_tw); }
+
 static int stats_finish(gs_plan* p, double* stats, void* stream) {
+    gs_plan::Deferred& d = p->defer;
     const long long n = (long long)p->nchains * p->nstat * p->ntile;
-    if (p->raw_pending) {
+    const int tmf = finish_tm(p);
+    if (d.raw_pending) {
         // raw sums: one workgroup per (chain, tile) sums them and applies the NC
         // operator of the sweep's D_l; the prologue's deferred draws ride in front
-        p->raw_pending = false;
-        const bool pro = p->pro_pending;
-        p->pro_pending = false;
-        const int nbp = pro ? nblk((long long)p->nchains * p->nspec * p->maxbins, 256) : 0;
-        const int nbu = pro && p->u_nat_ready ? nblk((long long)p->nchains * p->nacc, 256) : 0;
-        const int tmf = p->rows_per_task * (4 / p->sweep_tw);
+        d.raw_pending = false;
+        const bool pro = d.pro_pending;
+        const ProPre pp = take_pro(p);
         const long long nr = (long long)p->nchains * p->ntile;
-        const SweepOp op{GS_MODE_NONCENTERED, p->maxbins, p->raw_dl, p->ell2bin, p->bl, p->kappa[0], p->kappa[1],
+        const SweepOp op{GS_MODE_NONCENTERED, p->maxbins, d.raw_dl, p->ell2bin, p->bl, p->kappa[0], p->kappa[1],
                          p->kappa[2]};
-#define GS_FR(FF) hipLaunchKernelGGL((k_stats_finish_raw<FF>), dim3((unsigned)(nr + nbp + nbu)), dim3(256), 0,          \
-                                     S(stream), p->L, p->nchains, p->ntile, p->nchunkg, tmf, p->partials, p->dmom,      \
-                                     stats, op, nbp, nbu, p->u_nat, p->nspec, p->nacc, p->n_iter_mh, p->meta,           \
-                                     p->sd_tab(), p->sd_stride, p->pro_dl, p->prop, p->logr, p->pro_slo, p->pro_shi,    \
-                                     p->ita(p->pro_it), p->chain0, p->dl_tmp)
-        if (p->F == 1) GS_FR(1); else if (p->F == 2) GS_FR(2); else GS_FR(3);
-#undef GS_FR
+        with_F(p->F, [&](auto f) {
+            hipLaunchKernelGGL((k_stats_finish_raw<decltype(f)::value>), dim3((unsigned)(nr + pp.nbp + pp.nbu)),
+                               dim3(256), 0, S(stream), p->L, p->nchains, p->ntile, p->nchunkg, tmf, p->partials,
+                               p->dmom, stats, op, pp.nbp, pp.nbu, pp.u_out, pp.nspec, pp.nacc, pp.n_iter_mh, pp.nbins,
+                               pp.prop_sd, pp.sd_stride, pp.dl, pp.prop, pp.logr, d.pro_seed.lo, d.pro_seed.hi,
+                               p->ita(d.pro_it), p->chain0, pp.snap);
+        });
         GS_LAUNCH_CHECK("k_stats_finish_raw");
-        if (pro) p->snap_ok = true;
+        if (pro) d.snap_ok = true;
         return 0;
     }
-    if (p->pro_pending) {
+    if (d.pro_pending) {
         // the prologue's deferred draws in front of the partial sums
-        p->pro_pending = false;
-        const int nbp = nblk((long long)p->nchains * p->nspec * p->maxbins, 256);
-        const int nbu = p->u_nat_ready ? nblk((long long)p->nchains * p->nacc, 256) : 0;
-        const int tmf = p->rows_per_task * (4 / p->sweep_tw);
-#define GS_FP(FF, GG) hipLaunchKernelGGL((k_stats_finish_pro<FF, GG>), dim3((unsigned)(n + nbp + nbu)), dim3(256), 0,   \
-                                         S(stream), p->L, p->nchains, p->ntile, p->nchunkg, tmf, p->nstat, p->partials, \
-                                         stats, nbp, nbu, p->u_nat, p->nspec, p->nacc, p->n_iter_mh, p->maxbins,        \
-                                         p->meta, p->sd_tab(), p->sd_stride, p->pro_dl, p->prop, p->logr, p->pro_slo, p->pro_shi, \
-                                         p->ita(p->pro_it), p->chain0, p->dl_tmp)
-#define GS_FPG(FF) do { if (p->nchains <= 4) GS_FP(FF, 16); else GS_FP(FF, 4); } while (0)
-        if (p->F == 1) GS_FPG(1); else if (p->F == 2) GS_FPG(2); else GS_FPG(3);
-#undef GS_FPG
-#undef GS_FP
+        const ProPre pp = take_pro(p);
+        with_F(p->F, [&](auto f) {
+            with_G(p, [&](auto g) {
+                hipLaunchKernelGGL((k_stats_finish_pro<decltype(f)::value, decltype(g)::value>),
+                                   dim3((unsigned)(n + pp.nbp + pp.nbu)), dim3(256), 0, S(stream), p->L, p->nchains,
+                                   p->ntile, p->nchunkg, tmf, p->nstat, p->partials, stats, pp.nbp, pp.nbu, pp.u_out,
+                                   pp.nspec, pp.nacc, pp.n_iter_mh, pp.maxbins, pp.nbins, pp.prop_sd, pp.sd_stride,
+                                   pp.dl, pp.prop, pp.logr, d.pro_seed.lo, d.pro_seed.hi, p->ita(d.pro_it), p->chain0,
+                                   pp.snap);
+            });
+        });
         GS_LAUNCH_CHECK("k_stats_finish_pro");
-        p->snap_ok = true;
+        d.snap_ok = true;
         return 0;
     }
-    if (p->nchains <= 4)
-        hipLaunchKernelGGL(k_stats_finish<16>, dim3((unsigned)n), dim3(256), 0, S(stream), p->L, p->nchains, p->ntile,
-                           p->nchunkg, p->rows_per_task * (4 / p->sweep_tw), p->nstat, p->partials, stats);
-    else
-        hipLaunchKernelGGL(k_stats_finish<4>, dim3((unsigned)n), dim3(256), 0, S(stream), p->L, p->nchains, p->ntile,
-                           p->nchunkg, p->rows_per_task * (4 / p->sweep_tw), p->nstat, p->partials, stats);
+    with_G(p, [&](auto g) {
+        hipLaunchKernelGGL(k_stats_finish<decltype(g)::value>, dim3((unsigned)n), dim3(256), 0, S(stream), p->L,
+                           p->nchains, p->ntile, p->nchunkg, tmf, p->nstat, p->partials, stats);
+    });
     GS_LAUNCH_CHECK("k_stats_finish");
     return 0;
 }
 
-static int sweep_launch(gs_plan* p,const double* d_alm, const double* params, const double* z, uint64_t seed,
-                        uint32_t iteration, uint32_t substep, double* s_out, double* stats, bool given,
-                        void* stream, bool finish = true, int pmode = -1, const double* dl = nullptr,
-                        bool* cls_pre_done = nullptr, bool raw = false) {
+// ---- the CR sweep ------------------------------------------------------------
+// one sweep launch (plus, by default, the statistics finish)
+struct SweepReq {
+    const double* d_alm = nullptr;
+    // the operator: the parameter table, or computed per lane from dl
+    // (op_mode = GS_MODE_*), or none at all (given; raw without s_out)
+    const double* params = nullptr;
+    int op_mode = -1;
+    const double* dl = nullptr;      // the in-sweep operator's D_l; raw: the D_l the finish applies
+    const double* z = nullptr;       // replayed normals (null: native draws)
+    double* s_out = nullptr;         // the map to store (given: to read)
+    double* stats = nullptr;
+    bool given = false;              // the statistics of s_out as it is, no draw
+    bool raw = false;                // native NC draws accumulating raw moments
+    bool finish = true;              // the statistics finish after the sweep
+    SeedWords seed{0, 0};
+    uint32_t iteration = 0, substep = 0;
+    // non-null: the C_l draw's variates may ride in this launch (cls_var); set to whether they did
+    bool* cls_pre_done = nullptr;
+};
+
+static int sweep_launch(gs_plan* p, const SweepReq& r, void* stream) {
     if (check_plan(p)) return -1;
-    // raw: native NC draws accumulating raw moments (dl: the D_l the finish applies)
-    const bool raw_nost = raw && !s_out;        // no operator anywhere in the sweep
-    if (!d_alm || !stats || (!given && !params && pmode < 0 && !raw_nost) || (given && !s_out) ||
-        ((pmode >= 0 || raw) && !dl) || (raw && (given || z)))
+    const bool raw_nost = r.raw && !r.s_out;        // no operator anywhere in the sweep
+    if (!r.d_alm || !r.stats || (!r.given && !r.params && r.op_mode < 0 && !raw_nost) || (r.given && !r.s_out) ||
+        ((r.op_mode >= 0 || r.raw) && !r.dl) || (r.raw && (r.given || r.z)))
         return set_error("gs_cr_sweep: null argument");
-    p->raw_pending = raw;
-    p->raw_dl = raw ? dl : nullptr;
-    const SweepOp op{pmode, p->maxbins, dl, p->ell2bin, p->bl, p->kappa[0], p->kappa[1], p->kappa[2]};
-    const uint32_t slo = (uint32_t)(seed & 0xFFFFFFFFu), shi = (uint32_t)(seed >> 32);
+    p->defer.raw_pending = r.raw;
+    p->defer.raw_dl = r.raw ? r.dl : nullptr;
+    const SweepOp op{r.op_mode, p->maxbins, r.dl, p->ell2bin, p->bl, p->kappa[0], p->kappa[1], p->kappa[2]};
     const int nlog = (int)((long long)p->nchains * p->npair);
     dim3 g((unsigned)nlog), b(256);
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (timing_begin(p, S(stream), &e0, &e1)) return -1;
-    const bool rep = z != nullptr, st = s_out != nullptr;
+    const bool rep = r.z != nullptr, st = r.s_out != nullptr;
     // latency form (all loads first) for few chains with short tasks; the
     // throughput form otherwise (more chains: its registers buy occupancy)
-    const bool lat = pmode >= 0 && p->rows_per_task <= 4 && !given && !rep && p->sweep_latency;
-    const ClsPre none{};
-    if (cls_pre_done) *cls_pre_done = false;
-    if (lat) {
-        ClsPre cp{};
-        if (cls_pre_done && p->cls_pre) {
-            cp.nspec = p->nspec; cp.maxbins = p->maxbins; cp.bins = p->bins; cp.nbins = p->meta; cp.out = p->cls_var;
-            cp.nitem = p->nchains * p->nspec * p->maxbins;
-            cp.n = (cp.nitem + 255) / 256;
-            g.x += cp.n;
-            *cls_pre_done = true;
-        }
-#define GS_SWL(FF, SS) hipLaunchKernelGGL((k_cr_sweep<FF, 0, SS, 4>), g, b, 0, S(stream), p->L, p->nchains, p->ntile, \
-                                          p->nchunkg, p->rows_per_task, p->sweep_tw, p->tasks, d_alm, params, z,    \
-                                          s_out, p->partials, slo, shi, p->ita(iteration), substep, p->chain0, op, cp, \
-                                          ProPre{}, nlog)
-#define GS_SWLR(FF, SS) hipLaunchKernelGGL((k_cr_sweep<FF, 0, SS, 4, true>), g, b, 0, S(stream), p->L, p->nchains,      \
-                                           p->ntile, p->nchunkg, p->rows_per_task, p->sweep_tw, p->tasks, d_alm, params, \
-                                           z, s_out, p->partials, slo, shi, p->ita(iteration), substep, p->chain0, op,   \
-                                           cp, ProPre{}, nlog)
-#define GS_SWL2(FF) do { if (raw && st) GS_SWLR(FF, true); else if (raw) GS_SWLR(FF, false);                            \
-                         else if (st) GS_SWL(FF, true); else GS_SWL(FF, false); } while (0)
-        if (p->F == 1) GS_SWL2(1); else if (p->F == 2) GS_SWL2(2); else GS_SWL2(3);
-#undef GS_SWL2
-#undef GS_SWLR
-#undef GS_SWL
-        GS_LAUNCH_CHECK("k_cr_sweep");
-        if (p->timing && record_ev(e1, S(stream))) return -1;
-        return finish ? stats_finish(p, stats, stream) : 0;
-    }
-    // the prologue's deferred MH draws in front of this sweep (native, same step)
+    const bool lat = r.op_mode >= 0 && p->rows_per_task <= 4 && !r.given && !rep && p->sweep_latency;
+    ClsPre cp{};
     ProPre pp{};
-    if (cls_pre_done && p->cls_pre_many && !rep && !given && p->cls_var) {
-        // the C_l draw's variates in front workgroups (many chains, centered CR)
-        pp.cp.nspec = p->nspec; pp.cp.maxbins = p->maxbins; pp.cp.bins = p->bins; pp.cp.nbins = p->meta;
-        pp.cp.out = p->cls_var;
-        pp.cp.nitem = p->nchains * p->nspec * p->maxbins;
-        pp.nbv = (pp.cp.nitem + 255) / 256;
-        *cls_pre_done = true;
+    if (r.cls_pre_done) *r.cls_pre_done = false;
+    if (lat) {
+        // the C_l draw's variates in workgroups at the end of the grid (few chains)
+        if (r.cls_pre_done && p->cls_pre) {
+            cp = cls_front(p);
+            g.x += cp.n;
+            *r.cls_pre_done = true;
+        }
+    } else {
+        // the prologue's deferred MH draws in front of this sweep (native, same step)
+        if (p->defer.pro_pending && !rep && !r.given && r.iteration == p->defer.pro_it) {
+            pp = take_pro(p);
+            p->defer.snap_ok = true;
+        }
+        // the C_l draw's variates in front workgroups too (many chains, centered CR)
+        if (r.cls_pre_done && p->cls_pre_many && !rep && !r.given && p->cls_var) {
+            pp.cp = cls_front(p);
+            pp.nbv = pp.cp.n;
+            *r.cls_pre_done = true;
+        }
+        pp.n = (pp.nbp + pp.nbu + pp.nbv + 7) / 8 * 8;
+        g.x += pp.n;
     }
-    if (p->pro_pending && !rep && !given && iteration == p->pro_it) {
-        p->pro_pending = false;
-        p->snap_ok = true;
-        pp.nbp = nblk((long long)p->nchains * p->nspec * p->maxbins, 256);
-        pp.nbu = p->u_nat_ready ? nblk((long long)p->nchains * p->nacc, 256) : 0;
-        pp.nspec = p->nspec; pp.nacc = p->nacc; pp.n_iter_mh = p->n_iter_mh; pp.maxbins = p->maxbins;
-        pp.nbins = p->meta; pp.prop_sd = p->sd_tab(); pp.sd_stride = p->sd_stride; pp.dl = p->pro_dl;
-        pp.prop = p->prop; pp.logr = p->logr; pp.u_out = p->u_nat; pp.snap = p->dl_tmp;
-    }
-    pp.n = (pp.nbp + pp.nbu + pp.nbv + 7) / 8 * 8;
-    g.x += pp.n;
-#define GS_SW(FF, RR, SS) hipLaunchKernelGGL((k_cr_sweep<FF, RR, SS>), g, b, 0, S(stream), p->L, p->nchains, p->ntile, \
-                                             p->nchunkg, p->rows_per_task, p->sweep_tw, p->tasks, d_alm, params, z,   \
-                                             s_out,                                                                   \
-                                             p->partials, slo, shi, p->ita(iteration), substep, p->chain0, \
-                                             op, none, pp, nlog)
-#define GS_SWR(FF, SS) hipLaunchKernelGGL((k_cr_sweep<FF, 0, SS, 0, true>), g, b, 0, S(stream), p->L, p->nchains,       \
-                                          p->ntile, p->nchunkg, p->rows_per_task, p->sweep_tw, p->tasks, d_alm, params,  \
-                                          z, s_out, p->partials, slo, shi, p->ita(iteration), substep, p->chain0, op,    \
-                                          none, pp, nlog)
-#define GS_SWF(FF) do { if (given) GS_SW(FF, 2, false); else if (rep && st) GS_SW(FF, 1, true); \
-                        else if (rep) GS_SW(FF, 1, false); else if (raw && st) GS_SWR(FF, true);      \
-                        else if (raw) GS_SWR(FF, false); else if (st) GS_SW(FF, 0, true);             \
-                        else GS_SW(FF, 0, false); } while (0)
-    if (p->F == 1) GS_SWF(1); else if (p->F == 2) GS_SWF(2); else GS_SWF(3);
-#undef GS_SWF
-#undef GS_SWR
-#undef GS_SW
+    const SweepKernel k =
+        with_F(p->F, [&](auto f) { return sweep_variant<decltype(f)::value>(lat, r.given, rep, r.raw, st); });
+    hipLaunchKernelGGL(k, g, b, 0, S(stream), p->L, p->nchains, p->ntile, p->nchunkg, p->rows_per_task, p->sweep_tw,
+                       p->tasks, r.d_alm, r.params, r.z, r.s_out, p->partials, r.seed.lo, r.seed.hi,
+                       p->ita(r.iteration), r.substep, p->chain0, op, cp, pp, nlog);
     GS_LAUNCH_CHECK("k_cr_sweep");
     if (p->timing && record_ev(e1, S(stream))) return -1;
-    return finish ? stats_finish(p, stats, stream) : 0;
+    return r.finish ? stats_finish(p, r.stats, stream) : 0;
 }
 
 int gs_cr_sweep(gs_plan* p, const double* d_alm, const double* params, const double* z, uint64_t seed,
                 uint32_t iteration, uint32_t substep, double* s_out, double* stats, void* stream) {
-    return sweep_launch(p, d_alm, params, z, seed, iteration, substep, s_out, stats, false, stream);
+    SweepReq r;
+    r.d_alm = d_alm; r.params = params; r.z = z; r.s_out = s_out; r.stats = stats;
+    r.seed = seed_words(seed); r.iteration = iteration; r.substep = substep;
+    return sweep_launch(p, r, stream);
 }
 
 int gs_sweep_stats(gs_plan* p, const double* d_alm, const double* s, double* stats, void* stream) {
-    return sweep_launch(p, d_alm, nullptr, nullptr, 0, 0, 0, const_cast<double*>(s), stats, true, stream);
+    SweepReq r;
+    r.d_alm = d_alm; r.s_out = const_cast<double*>(s); r.stats = stats; r.given = true;
+    return sweep_launch(p, r, stream);
 }
 
 static int cls_draw_launch(gs_plan* p, const double* stats, const double* variates, uint64_t seed,
@@ -2993,45 +3048,170 @@ static int cls_draw_launch(gs_plan* p, const double* stats, const double* variat
                            void* stream, const double* pre = nullptr) {
     if (check_plan(p)) return -1;
     if (!stats || !dl_out) return set_error("gs_cls_draw: null argument");
-    const uint32_t slo = (uint32_t)(seed & 0xFFFFFFFFu), shi = (uint32_t)(seed >> 32);
+    const SeedWords sw = seed_words(seed);
     const dim3 g(p->nchains, p->nspec, (p->maxbins + 63) / 64), b(64);
-#define GS_CD(FF) hipLaunchKernelGGL((k_cls_draw<FF>), g, b, 0, S(stream), p->L, p->nchains, p->maxbins, p->bins, p->meta, \
-                                     stats, variates, slo, shi, p->ita(iteration), p->chain0, dl_out, trace, \
-                                     cap, counter, p->graph_adv, pre)
-    if (p->F == 1) GS_CD(1); else if (p->F == 2) GS_CD(2); else GS_CD(3);
-#undef GS_CD
+    with_F(p->F, [&](auto f) {
+        hipLaunchKernelGGL((k_cls_draw<decltype(f)::value>), g, b, 0, S(stream), p->L, p->nchains, p->maxbins, p->bins,
+                           p->meta, stats, variates, sw.lo, sw.hi, p->ita(iteration), p->chain0, dl_out, trace, cap,
+                           counter, p->graph_adv, pre);
+    });
     GS_LAUNCH_CHECK("k_cls_draw");
     return 0;
 }
-
 
 int gs_cls_draw(gs_plan* p, const double* stats, const double* variates, uint64_t seed, uint32_t iteration,
                 double* dl_out, void* stream) {
     return cls_draw_launch(p, stats, variates, seed, iteration, dl_out, nullptr, 1, nullptr, stream);
 }
 
-static int mh_decide(gs_plan* p, const double* stats, double* dl, const double* u_acc, uint32_t slo, uint32_t shi,
-                     uint32_t iteration, int32_t* accept_out, void* stream, const MhEpi* epi = nullptr);
+// ---- Metropolis-Hastings -------------------------------------------------------
+// one workgroup's phases from a set of plan tables: the whole chain's (own = -1)
+// or one kind of the split form's
+static MhPhases mh_phases(int nphase, int lmin, int own, const int (*sp)[2], const int* off, const int* cnt,
+                          const int* nwide) {
+    MhPhases h{};
+    h.nphase = nphase;
+    h.lmin = lmin;
+    h.own = own;
+    for (int q = 0; q < 4; ++q) {
+        const bool on = q < nphase;
+        h.sp0[q] = on ? sp[q][0] : -1; h.sp1[q] = on ? sp[q][1] : -1;
+        h.off[q] = on ? off[q] : 0; h.n[q] = on ? cnt[q] : 0; h.nwide[q] = on ? nwide[q] : 0;
+    }
+    return h;
+}
+
+// the MH phases proper (proposals already in p->prop / p->logr)
+static int mh_decide(gs_plan* p, const double* stats, double* dl, const double* u_acc, SeedWords sw,
+                     uint32_t iteration, int32_t* accept_out, void* stream, const MhEpi* epi = nullptr) {
+    const MhEpi none{nullptr, 1, nullptr, p->nchains, 0, nullptr};
+    MhEpi E = epi ? *epi : none;
+    // the proposal launch's D_l snapshot belongs to this decision only
+    const bool snap = p->defer.snap_ok;
+    p->defer.snap_ok = false;
+    int maxnb = 0, ntab = 0;
+    for (int q = 0; q < p->nphase; ++q) {
+        maxnb = std::max(maxnb, p->phase_n[q]);
+        ntab += p->phase_n[q];
+    }
+    const size_t lds = (2 * (size_t)(p->L + 1) + (size_t)maxnb * p->n_iter_mh + (size_t)p->nspec * p->maxbins) *
+                           sizeof(double) + (size_t)p->nspec * (p->L + 1) * sizeof(int);
+    const size_t lds_u = u_acc ? (size_t)p->nacc * sizeof(double) : 0;
+    // r03: the register / LDS-resident form when the phase l range is at most
+    // one l per thread and its arrays fit the LDS (k_mh_fused otherwise)
+    const size_t lds_reg = (2 * (size_t)(p->L + 1) + (size_t)p->nacc + 3 * (size_t)p->nspec * p->maxbins) *
+                           sizeof(double) + 16 + (size_t)ntab * (sizeof(int4) + sizeof(int2));
+    const bool reg = p->L + 1 - p->mh_lmin <= MH_REG_THREADS && lds_reg <= 150 * 1024;
+    if (!reg && E.dl_in) {
+        // the older MH forms read and write dl in place: copy the input first
+        const size_t bytes = (size_t)p->nchains * p->nspec * p->maxbins * sizeof(double);
+        GS_CHECK(hipMemcpyAsync(dl, E.dl_in, bytes, hipMemcpyDeviceToDevice, S(stream)));
+        E.dl_in = nullptr;
+    }
+    // the split form (two workgroups per chain): both workgroups of a chain read
+    // its start D_l, the T / E one writes its rows of dl at its end, so neither
+    // may read dl itself -- the BB workgroup's PSD test of the T / E state would
+    // depend on the order the two run in (ADVICE r05).  They read a stable copy:
+    // the caller's dl_in (ASIS: the drawn D_l) or the snapshot the proposal
+    // launch wrote (dl_tmp); without either the chain runs in one workgroup.
+    bool split = reg && p->mh_split && p->ntab_s > 0;
+    if (split && !E.dl_in) {
+        if (snap) E.dl_in = p->dl_tmp;
+        else split = false;
+    }
+    MhPhases ph = mh_phases(p->nphase, p->mh_lmin, -1, p->phase_sp, p->phase_off, p->phase_n, p->phase_nwide), ph1{};
+    if (split) {
+        // kind 0 the T / E phases (and the rows of no MH spectrum), kind 1 [BB]
+        ph = mh_phases(p->sph_n[0], p->mh_lmin, ~p->sph_own[1], p->sph_sp[0], p->sph_off[0], p->sph_cnt[0],
+                       p->sph_nwide[0]);
+        ph1 = mh_phases(p->sph_n[1], p->mh_lmin, p->sph_own[1], p->sph_sp[1], p->sph_off[1], p->sph_cnt[1],
+                        p->sph_nwide[1]);
+    }
+    if (reg) {
+        static bool attr_set[4] = {false, false, false, false};
+        const int nwg = split ? 2 : 1;
+        const int rc = with_F(p->F, [&](auto f) -> int {
+            constexpr int F = decltype(f)::value;
+            if (!attr_set[F])
+                GS_CHECK(hipFuncSetAttribute((const void*)k_mh_reg<F>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             150 * 1024));
+            attr_set[F] = true;
+            hipLaunchKernelGGL((k_mh_reg<F>), dim3(p->nchains * nwg), dim3(MH_REG_THREADS), lds_reg, S(stream), p->L,
+                               p->maxbins, ph, split ? p->ntab_s : ntab, split ? p->phase_tab_s : p->phase_tab,
+                               split ? p->phase_rng_s : p->phase_rng, p->meta, p->nacc, p->n_iter_mh, p->ell2blk,
+                               p->ell2bin, p->bl, p->kappa[0], p->kappa[1], p->kappa[2], stats, dl, p->prop, p->logr,
+                               u_acc, sw.lo, sw.hi, p->ita(iteration), p->chain0, accept_out, E, ph1, nwg);
+            return 0;
+        });
+        if (rc) return rc;
+        GS_LAUNCH_CHECK("k_mh_reg");
+        return 0;
+    }
+    if (lds <= 128 * 1024) {
+        with_F(p->F, [&](auto f) {
+            hipLaunchKernelGGL((k_mh_fused<decltype(f)::value>), dim3(p->nchains), dim3(1024), lds + lds_u, S(stream),
+                               p->L, p->maxbins, ph, p->phase_tab, p->phase_rng, p->bins, p->blocks, p->meta + 8,
+                               p->nacc, p->n_iter_mh, p->ell2blk, p->ell2bin, p->bl, p->kappa[0], p->kappa[1],
+                               p->kappa[2], stats, dl, p->prop, p->logr, u_acc, sw.lo, sw.hi, p->ita(iteration),
+                               p->chain0, accept_out, E);
+        });
+        GS_LAUNCH_CHECK("k_mh_fused");
+        return 0;
+    }
+    if (epi) return set_error("mh_decide: the fused epilogue needs the single-launch MH (l_max too large)");
+    // very large l_max: two launches per phase (terms in HBM, one wave per block)
+    const long long nl = (long long)p->nchains * (p->L + 1);
+    for (int q = 0; q < p->nphase; ++q) {
+        const int nb = p->phase_n[q];
+        if (nb == 0) continue;
+        const int sp0 = p->phase_sp[q][0], sp1 = p->phase_sp[q][1];
+        with_F(p->F, [&](auto f) {
+            hipLaunchKernelGGL((k_mh_terms<decltype(f)::value>), dim3(nblk(nl, 256)), dim3(256), 0, S(stream), p->L,
+                               p->nchains, p->maxbins, sp0, sp1, p->ell2blk, p->ell2bin, p->bl, p->kappa[0],
+                               p->kappa[1], p->kappa[2], stats, dl, p->prop, p->gbuf);
+        });
+        GS_LAUNCH_CHECK("k_mh_terms");
+        const long long waves = (long long)p->nchains * nb;
+        const int2* tab = p->phase_tab + p->phase_off[q];
+        with_F(p->F, [&](auto f) {
+            hipLaunchKernelGGL((k_mh_accept<decltype(f)::value>), dim3(nblk(waves, 4)), dim3(256), 0, S(stream), p->L,
+                               p->nchains, p->maxbins, sp0, p->bins, p->blocks, tab, nb, p->meta + 8, p->nacc,
+                               p->n_iter_mh, p->gbuf, dl, p->prop, p->logr, u_acc, sw.lo, sw.hi, p->ita(iteration),
+                               p->chain0, accept_out);
+        });
+        GS_LAUNCH_CHECK("k_mh_accept");
+    }
+    return 0;
+}
+
+// the proposals and log-ratios of every (chain, spectrum, bin) from dl;
+// snapshot: dl also copied to dl_tmp (the split MH's start state)
+static int mh_propose_launch(gs_plan* p, const double* dl, double* prop, double* logr, const double* u_prop,
+                             SeedWords sw, uint32_t iteration, bool snapshot, void* stream) {
+    const long long nprop = (long long)p->nchains * p->nspec * p->maxbins;
+    with_F(p->F, [&](auto f) {
+        hipLaunchKernelGGL((k_mh_propose<decltype(f)::value>), dim3(nblk(nprop, 256)), dim3(256), 0, S(stream),
+                           p->nchains, p->maxbins, p->meta, p->sd_tab(), p->sd_stride, dl, prop, logr, u_prop, sw.lo,
+                           sw.hi, p->ita(iteration), p->chain0, snapshot ? p->dl_tmp : nullptr);
+    });
+    GS_LAUNCH_CHECK("k_mh_propose");
+    return 0;
+}
 
 int gs_mh_propose(gs_plan* p, const double* dl, const double* u_prop, uint64_t seed, uint32_t iteration,
                   double* prop_out, double* logr_out, double* u_acc_out, void* stream) {
     if (check_plan(p)) return -1;
     if (!p->has_mh) return set_error("gs_mh_propose: plan has no MH blocks / proposal variances");
     if (!dl || !prop_out || !logr_out) return set_error("gs_mh_propose: null argument");
-    const uint32_t slo = (uint32_t)(seed & 0xFFFFFFFFu), shi = (uint32_t)(seed >> 32);
+    const SeedWords sw = seed_words(seed);
     const long long nprop = (long long)p->nchains * p->nspec * p->maxbins;
     GS_CHECK(hipMemsetAsync(prop_out, 0, nprop * sizeof(double), S(stream)));
     GS_CHECK(hipMemsetAsync(logr_out, 0, nprop * sizeof(double), S(stream)));
-#define GS_MP(FF) hipLaunchKernelGGL((k_mh_propose<FF>), dim3(nblk(nprop, 256)), dim3(256), 0, S(stream), p->nchains, \
-                                     p->maxbins, p->meta, p->sd_tab(), p->sd_stride, dl, prop_out, logr_out, u_prop, slo, shi, \
-                                     p->ita(iteration), p->chain0, nullptr)
-    if (p->F == 1) GS_MP(1); else if (p->F == 2) GS_MP(2); else GS_MP(3);
-#undef GS_MP
-    GS_LAUNCH_CHECK("k_mh_propose");
+    if (mh_propose_launch(p, dl, prop_out, logr_out, u_prop, sw, iteration, false, stream)) return -1;
     if (u_acc_out) {
         const long long n = (long long)p->nchains * p->nacc;
         hipLaunchKernelGGL(k_mh_uniforms, dim3(nblk(n, 256)), dim3(256), 0, S(stream), p->nchains, p->nspec,
-                           p->maxbins, p->meta, p->nacc, p->n_iter_mh, slo, shi, p->ita(iteration),
+                           p->maxbins, p->meta, p->nacc, p->n_iter_mh, sw.lo, sw.hi, p->ita(iteration),
                            p->chain0, u_acc_out);
         GS_LAUNCH_CHECK("k_mh_uniforms");
     }
@@ -3043,16 +3223,10 @@ int gs_nc_mh(gs_plan* p, const double* stats, double* dl, const double* u_prop, 
     if (check_plan(p)) return -1;
     if (!p->has_mh) return set_error("gs_nc_mh: plan has no MH blocks / proposal variances");
     if (!stats || !dl) return set_error("gs_nc_mh: null argument");
-    const uint32_t slo = (uint32_t)(seed & 0xFFFFFFFFu), shi = (uint32_t)(seed >> 32);
-    const long long nprop = (long long)p->nchains * p->nspec * p->maxbins;
-#define GS_MP(FF) hipLaunchKernelGGL((k_mh_propose<FF>), dim3(nblk(nprop, 256)), dim3(256), 0, S(stream), p->nchains, \
-                                     p->maxbins, p->meta, p->sd_tab(), p->sd_stride, dl, p->prop, p->logr, u_prop, slo, shi, p->ita(iteration), \
-                                     p->chain0, p->dl_tmp)
-    if (p->F == 1) GS_MP(1); else if (p->F == 2) GS_MP(2); else GS_MP(3);
-#undef GS_MP
-    GS_LAUNCH_CHECK("k_mh_propose");
-    p->snap_ok = true;
-    return mh_decide(p, stats, dl, u_acc, slo, shi, iteration, accept_out, stream);
+    const SeedWords sw = seed_words(seed);
+    if (mh_propose_launch(p, dl, p->prop, p->logr, u_prop, sw, iteration, true, stream)) return -1;
+    p->defer.snap_ok = true;
+    return mh_decide(p, stats, dl, u_acc, sw, iteration, accept_out, stream);
 }
 
 // ---- warm-up adaptation of the proposal scales ------------------------------
@@ -3135,138 +3309,20 @@ int gs_mh_proposal_sd(gs_plan* p, double* sd_out, void* stream) {
     return 0;
 }
 
-// the MH phases proper (proposals already in p->prop / p->logr)
-static int mh_decide(gs_plan* p, const double* stats, double* dl, const double* u_acc, uint32_t slo, uint32_t shi,
-                     uint32_t iteration, int32_t* accept_out, void* stream, const MhEpi* epi) {
-    int maxnb = 0;
-    const MhEpi none{nullptr, 1, nullptr, p->nchains, 0, nullptr};
-    MhEpi E = epi ? *epi : none;
-    // the proposal launch's D_l snapshot belongs to this decision only
-    const bool snap = p->snap_ok;
-    p->snap_ok = false;
-    MhPhases ph{};
-    ph.nphase = p->nphase;
-    ph.lmin = p->mh_lmin;
-    ph.own = -1;
-    for (int q = 0; q < 4; ++q) {
-        ph.sp0[q] = p->phase_sp[q][0]; ph.sp1[q] = p->phase_sp[q][1];
-        ph.off[q] = p->phase_off[q]; ph.n[q] = p->phase_n[q]; ph.nwide[q] = p->phase_nwide[q];
-        maxnb = std::max(maxnb, p->phase_n[q]);
-    }
-    const size_t lds = (2 * (size_t)(p->L + 1) + (size_t)maxnb * p->n_iter_mh + (size_t)p->nspec * p->maxbins) *
-                           sizeof(double) + (size_t)p->nspec * (p->L + 1) * sizeof(int);
-    const size_t lds_u = u_acc ? (size_t)p->nacc * sizeof(double) : 0;
-    // r03: the register / LDS-resident form when the phase l range is at most
-    // one l per thread and its arrays fit the LDS (k_mh_fused otherwise)
-    int ntab = 0;
-    for (int q = 0; q < p->nphase; ++q) ntab += p->phase_n[q];
-    const size_t lds_reg = (2 * (size_t)(p->L + 1) + (size_t)p->nacc + 3 * (size_t)p->nspec * p->maxbins) *
-                           sizeof(double) + 16 + (size_t)ntab * (sizeof(int4) + sizeof(int2));
-    const bool reg = p->L + 1 - p->mh_lmin <= MH_REG_THREADS && lds_reg <= 150 * 1024;
-    if (!reg && E.dl_in) {
-        // the older MH forms read and write dl in place: copy the input first
-        const size_t bytes = (size_t)p->nchains * p->nspec * p->maxbins * sizeof(double);
-        GS_CHECK(hipMemcpyAsync(dl, E.dl_in, bytes, hipMemcpyDeviceToDevice, S(stream)));
-        E.dl_in = nullptr;
-    }
-    // the split form (two workgroups per chain): both workgroups of a chain read
-    // its start D_l, the T / E one writes its rows of dl at its end, so neither
-    // may read dl itself -- the BB workgroup's PSD test of the T / E state would
-    // depend on the order the two run in (ADVICE r05).  They read a stable copy:
-    // the caller's dl_in (ASIS: the drawn D_l) or the snapshot the proposal
-    // launch wrote (dl_tmp); without either the chain runs in one workgroup.
-    bool split = reg && p->mh_split && p->ntab_s > 0;
-    if (split && !E.dl_in) {
-        if (snap) E.dl_in = p->dl_tmp;
-        else split = false;
-    }
-    MhPhases ph1{};
-    if (split) {
-        MhPhases* k2[2] = {&ph, &ph1};
-        for (int k = 0; k < 2; ++k) {
-            MhPhases& h = *k2[k];
-            h = MhPhases{};
-            h.nphase = p->sph_n[k];
-            h.lmin = p->mh_lmin;
-            h.own = k == 0 ? ~p->sph_own[1] : p->sph_own[1];
-            for (int q = 0; q < 4; ++q) {
-                const bool on = q < h.nphase;
-                h.sp0[q] = on ? p->sph_sp[k][q][0] : -1; h.sp1[q] = -1;
-                h.off[q] = on ? p->sph_off[k][q] : 0; h.n[q] = on ? p->sph_cnt[k][q] : 0;
-                h.nwide[q] = on ? p->sph_nwide[k][q] : 0;
-            }
-        }
-    }
-    if (reg) {
-        static bool attr_set[4] = {false, false, false, false};
-#define GS_MR(FF) do {                                                                                                 \
-        if (!attr_set[FF])                                                                                             \
-            GS_CHECK(hipFuncSetAttribute((const void*)k_mh_reg<FF>, hipFuncAttributeMaxDynamicSharedMemorySize,       \
-                                         150 * 1024));                                                                 \
-        attr_set[FF] = true;                                                                                           \
-        hipLaunchKernelGGL((k_mh_reg<FF>), dim3(p->nchains * (split ? 2 : 1)), dim3(MH_REG_THREADS), lds_reg, S(stream), \
-                           p->L, p->maxbins, ph, split ? p->ntab_s : ntab, split ? p->phase_tab_s : p->phase_tab,          \
-                           split ? p->phase_rng_s : p->phase_rng, p->meta, p->nacc, p->n_iter_mh, p->ell2blk,           \
-                           p->ell2bin, p->bl, p->kappa[0], p->kappa[1], p->kappa[2], stats, dl, p->prop, p->logr,      \
-                           u_acc, slo, shi, p->ita(iteration), p->chain0, accept_out, E, ph1, split ? 2 : 1); } while (0)
-        if (p->F == 1) GS_MR(1); else if (p->F == 2) GS_MR(2); else GS_MR(3);
-#undef GS_MR
-        GS_LAUNCH_CHECK("k_mh_reg");
-        return 0;
-    }
-    if (lds <= 128 * 1024) {
-#define GS_MF(FF) hipLaunchKernelGGL((k_mh_fused<FF>), dim3(p->nchains), dim3(1024), lds + lds_u, S(stream), p->L, p->maxbins, ph, \
-                                     p->phase_tab, p->phase_rng, p->bins, p->blocks, p->meta + 8, p->nacc, p->n_iter_mh, p->ell2blk,    \
-                                     p->ell2bin, p->bl, p->kappa[0], p->kappa[1], p->kappa[2], stats, dl, p->prop,       \
-                                     p->logr, u_acc, slo, shi, p->ita(iteration), p->chain0, accept_out, E)
-        if (p->F == 1) { GS_MF(1); } else if (p->F == 2) { GS_MF(2); } else { GS_MF(3); }
-#undef GS_MF
-        GS_LAUNCH_CHECK("k_mh_fused");
-        return 0;
-    }
-    if (epi) return set_error("mh_decide: the fused epilogue needs the single-launch MH (l_max too large)");
-    // very large l_max: two launches per phase (terms in HBM, one wave per block)
-    const long long nl = (long long)p->nchains * (p->L + 1);
-    for (int ph = 0; ph < p->nphase; ++ph) {
-        const int nb = p->phase_n[ph];
-        if (nb == 0) continue;
-        const int sp0 = p->phase_sp[ph][0], sp1 = p->phase_sp[ph][1];
-#define GS_MT(FF) hipLaunchKernelGGL((k_mh_terms<FF>), dim3(nblk(nl, 256)), dim3(256), 0, S(stream), p->L, p->nchains, \
-                                     p->maxbins, sp0, sp1, p->ell2blk, p->ell2bin, p->bl, p->kappa[0], p->kappa[1],  \
-                                     p->kappa[2], stats, dl, p->prop, p->gbuf)
-        if (p->F == 1) GS_MT(1); else if (p->F == 2) GS_MT(2); else GS_MT(3);
-#undef GS_MT
-        GS_LAUNCH_CHECK("k_mh_terms");
-        const long long waves = (long long)p->nchains * nb;
-        const int2* tab = p->phase_tab + p->phase_off[ph];
-#define GS_MA(FF) hipLaunchKernelGGL((k_mh_accept<FF>), dim3(nblk(waves, 4)), dim3(256), 0, S(stream), p->L, p->nchains, \
-                                     p->maxbins, sp0, p->bins, p->blocks, tab, nb, p->meta + 8, p->nacc, p->n_iter_mh, \
-                                     p->gbuf, dl, p->prop, p->logr, u_acc, slo, shi, p->ita(iteration), p->chain0, accept_out)
-        if (p->F == 1) GS_MA(1); else if (p->F == 2) GS_MA(2); else GS_MA(3);
-#undef GS_MA
-        GS_LAUNCH_CHECK("k_mh_accept");
-    }
-    return 0;
-}
-
 // pro: also the MH proposals from dl (native draws) in front workgroups
 static int stats_to_nc_launch(gs_plan* p, const double* dl, double* stats, void* stream, bool pro = false,
-                              uint64_t seed = 0, uint32_t it = 0) {
+                              SeedWords sw = {0, 0}, uint32_t it = 0) {
     const long long n = (long long)p->nchains * (p->L + 1);
     ProPre pp{};
     if (pro) {
-        pp.nbp = nblk((long long)p->nchains * p->nspec * p->maxbins, 256);
+        pp = pro_front(p, dl, false, false);
         pp.n = pp.nbp;
-        pp.nspec = p->nspec; pp.nacc = p->nacc; pp.n_iter_mh = p->n_iter_mh; pp.maxbins = p->maxbins;
-        pp.nbins = p->meta; pp.prop_sd = p->sd_tab(); pp.sd_stride = p->sd_stride; pp.dl = dl; pp.prop = p->prop;
-        pp.logr = p->logr;
     }
-    const uint32_t slo = (uint32_t)(seed & 0xFFFFFFFFu), shi = (uint32_t)(seed >> 32);
-#define GS_TN(FF) hipLaunchKernelGGL((k_stats_to_nc<FF>), dim3(nblk(n, 256) + (unsigned)pp.n), dim3(256), 0, S(stream), \
-                                     p->L, p->nchains, p->maxbins, dl, p->ell2bin, stats, pp, slo, shi, p->ita(it),     \
-                                     p->chain0)
-    if (p->F == 1) GS_TN(1); else if (p->F == 2) GS_TN(2); else GS_TN(3);
-#undef GS_TN
+    with_F(p->F, [&](auto f) {
+        hipLaunchKernelGGL((k_stats_to_nc<decltype(f)::value>), dim3(nblk(n, 256) + (unsigned)pp.n), dim3(256), 0,
+                           S(stream), p->L, p->nchains, p->maxbins, dl, p->ell2bin, stats, pp, sw.lo, sw.hi, p->ita(it),
+                           p->chain0);
+    });
     GS_LAUNCH_CHECK("k_stats_to_nc");
     return 0;
 }
@@ -3281,10 +3337,10 @@ int gs_recentre(gs_plan* p, const double* dl_new, const double* dl_old, double* 
     if (check_plan(p)) return -1;
     if (!dl_new || !s) return set_error("gs_recentre: null argument");
     const long long n = (long long)p->nchains * (p->L + 1) * (p->L + 2) / 2;
-#define GS_RC(FF) hipLaunchKernelGGL((k_recentre<FF>), dim3(nblk(n, 256)), dim3(256), 0, S(stream), p->L, p->nchains, \
-                                     p->maxbins, dl_new, dl_old, p->ell2bin, s)
-    if (p->F == 1) GS_RC(1); else if (p->F == 2) GS_RC(2); else GS_RC(3);
-#undef GS_RC
+    with_F(p->F, [&](auto f) {
+        hipLaunchKernelGGL((k_recentre<decltype(f)::value>), dim3(nblk(n, 256)), dim3(256), 0, S(stream), p->L,
+                           p->nchains, p->maxbins, dl_new, dl_old, p->ell2bin, s);
+    });
     GS_LAUNCH_CHECK("k_recentre");
     return 0;
 }
@@ -3292,14 +3348,20 @@ int gs_recentre(gs_plan* p, const double* dl_new, const double* dl_old, double* 
 // the CR of a step: block parameters of dl (mode) + the sweep, the operator
 // either from the parameter table (many chains) or computed inside the sweep
 static int step_sweep(gs_plan* p, int mode, const double* d_alm, const double* dl, const double* z, uint64_t seed,
-                      uint32_t it, double* s_out, void* stream, bool finish = true, bool* cls_pre_done = nullptr) {
+                      uint32_t it, double* s_out, void* stream, bool* cls_pre_done = nullptr) {
     if (cls_pre_done) *cls_pre_done = false;
-    if (p->inkernel_params)
-        return sweep_launch(p, d_alm, nullptr, z, seed, it, 0, s_out, p->stats, false, stream, finish, mode, dl,
-                            cls_pre_done);
-    if (gs_block_params(p, mode, dl, p->params, stream)) return -1;
-    return sweep_launch(p, d_alm, p->params, z, seed, it, 0, s_out, p->stats, false, stream, finish, -1, nullptr,
-                        mode == GS_MODE_CENTERED ? cls_pre_done : nullptr);
+    SweepReq r;
+    r.d_alm = d_alm; r.z = z; r.s_out = s_out; r.stats = p->stats;
+    r.seed = seed_words(seed); r.iteration = it;
+    if (p->inkernel_params) {
+        r.op_mode = mode; r.dl = dl;
+        r.cls_pre_done = cls_pre_done;
+    } else {
+        if (gs_block_params(p, mode, dl, p->params, stream)) return -1;
+        r.params = p->params;
+        r.cls_pre_done = mode == GS_MODE_CENTERED ? cls_pre_done : nullptr;
+    }
+    return sweep_launch(p, r, stream);
 }
 
 // ---- fused iterations ------------------------------------------------------
@@ -3309,8 +3371,7 @@ int gs_step_centered(gs_plan* p, const double* d_alm, double* dl, double* s_out,
     if (check_plan(p)) return -1;
     if (!d_alm || !dl) return set_error("gs_step_centered: null argument");
     bool pre = false;
-    if (step_sweep(p, GS_MODE_CENTERED, d_alm, dl, z, seed, it, s_out, stream, true, igvar ? nullptr : &pre))
-        return -1;
+    if (step_sweep(p, GS_MODE_CENTERED, d_alm, dl, z, seed, it, s_out, stream, igvar ? nullptr : &pre)) return -1;
     return cls_draw_launch(p, p->stats, igvar, seed, it, dl, nullptr, 1, nullptr, stream, pre ? p->cls_var : nullptr);
 }
 
@@ -3321,7 +3382,7 @@ int gs_step_centered_fused(gs_plan* p, const double* d_alm, double* dl, double* 
     if (trace && capacity < 1) return set_error("gs_step_centered_fused: capacity < 1");
     if (!d_alm || !dl) return set_error("gs_step_centered_fused: null argument");
     bool pre = false;
-    if (step_sweep(p, GS_MODE_CENTERED, d_alm, dl, nullptr, seed, it, s_out, stream, true, &pre)) return -1;
+    if (step_sweep(p, GS_MODE_CENTERED, d_alm, dl, nullptr, seed, it, s_out, stream, &pre)) return -1;
     return cls_draw_launch(p, p->stats, nullptr, seed, it, dl, trace, trace ? capacity : 1, p->adv_counter(), stream,
                            pre ? p->cls_var : nullptr);
 }
@@ -3330,54 +3391,48 @@ int gs_nc_prologue(gs_plan* p, const double* dl, const double* u_prop, uint64_t 
     if (check_plan(p)) return -1;
     if (!p->has_mh) return set_error("gs_nc_prologue: plan has no MH blocks / proposal variances");
     if (!dl) return set_error("gs_nc_prologue: null argument");
-    const uint32_t slo = (uint32_t)(seed & 0xFFFFFFFFu), shi = (uint32_t)(seed >> 32);
-    const int nbp = nblk((long long)p->nchains * p->nspec * p->maxbins, 256);
+    gs_plan::Deferred& d = p->defer;
+    const SeedWords sw = seed_words(seed);
     // block parameters here (table) unless the sweep computes them per lane
     const int nbq = p->inkernel_params ? 0 : nblk((long long)p->nchains * (p->L + 1), 256);
     // native mode: the MH accept uniforms are drawn here too (replay draws them on the host)
-    p->u_nat_ready = u_prop == nullptr && p->nacc > 0;
-    const int nbu = p->u_nat_ready ? nblk((long long)p->nchains * p->nacc, 256) : 0;
-    p->snap_ok = false;
-    if (u_prop == nullptr && (nbq > 0 || p->nchains > 4)) {
+    d.u_nat_ready = u_prop == nullptr && p->nacc > 0;
+    d.snap_ok = false;
+    ProPre pp = pro_front(p, dl, true, d.u_nat_ready);
+    const bool deferred = u_prop == nullptr && (nbq > 0 || p->nchains > 4);
+    if (deferred) {
         // native draws: to the front of this step's sweep (or statistics finish)
-        p->pro_pending = true;
-        p->pro_dl = dl; p->pro_slo = slo; p->pro_shi = shi; p->pro_it = it;
+        d.pro_pending = true;
+        d.pro_dl = dl; d.pro_seed = sw; d.pro_it = it;
         if (nbq == 0) return 0;                   // the sweep computes the operator: no launch
         if (p->raw_on) {
             // the parameter table waits for gs_nc_sweep: a raw-moment sweep that
             // stores no map reads no operator, and the step has no prologue launch
-            p->par_pending = true;
-            p->par_dl = dl;
+            d.par_pending = true;
+            d.par_dl = dl;
             return 0;
         }
-#define GS_PRQ(FF) hipLaunchKernelGGL((k_nc_prologue<FF>), dim3(nbq), dim3(256), 0, S(stream), 0, nbq, p->u_nat,     \
-                                      p->nspec, p->nacc, p->n_iter_mh, p->L, p->nchains, p->maxbins, p->ell2bin, p->bl, \
-                                      p->kappa[0], p->kappa[1], p->kappa[2], p->params, p->meta, p->sd_tab(), p->sd_stride, dl, \
-                                      p->prop, p->logr, u_prop, slo, shi, p->ita(it), p->chain0, nullptr)
-        if (p->F == 1) GS_PRQ(1); else if (p->F == 2) GS_PRQ(2); else GS_PRQ(3);
-#undef GS_PRQ
-        GS_LAUNCH_CHECK("k_nc_prologue");
-        return 0;
+        pp.nbp = pp.nbu = 0;                      // this launch: the parameter table alone
+    } else {
+        d.pro_pending = false;
+        d.par_pending = false;
     }
-    p->pro_pending = false;
-    p->par_pending = false;
-#define GS_PRO(FF) hipLaunchKernelGGL((k_nc_prologue<FF>), dim3(nbp + nbq + nbu), dim3(256), 0, S(stream), nbp, nbq,   \
-                                      p->u_nat, p->nspec, p->nacc, p->n_iter_mh, p->L,                                  \
-                                      p->nchains, p->maxbins, p->ell2bin, p->bl, p->kappa[0], p->kappa[1], p->kappa[2], \
-                                      p->params, p->meta, p->sd_tab(), p->sd_stride, dl, p->prop, p->logr, u_prop, slo, shi, \
-                                      p->ita(it), p->chain0, p->dl_tmp)
-    if (p->F == 1) GS_PRO(1); else if (p->F == 2) GS_PRO(2); else GS_PRO(3);
-#undef GS_PRO
+    with_F(p->F, [&](auto f) {
+        hipLaunchKernelGGL((k_nc_prologue<decltype(f)::value>), dim3(pp.nbp + nbq + pp.nbu), dim3(256), 0, S(stream),
+                           pp.nbp, nbq, pp.u_out, pp.nspec, pp.nacc, pp.n_iter_mh, p->L, p->nchains, pp.maxbins,
+                           p->ell2bin, p->bl, p->kappa[0], p->kappa[1], p->kappa[2], p->params, pp.nbins, pp.prop_sd,
+                           pp.sd_stride, pp.dl, pp.prop, pp.logr, u_prop, sw.lo, sw.hi, p->ita(it), p->chain0, pp.snap);
+    });
     GS_LAUNCH_CHECK("k_nc_prologue");
-    p->snap_ok = true;
+    if (!deferred) d.snap_ok = true;
     return 0;
 }
 
 static int data_moments_launch(gs_plan* p, const double* d_alm, void* stream) {
-#define GS_DM(FF) hipLaunchKernelGGL((k_data_moments<FF>), dim3(nblk(p->L + 1, 64)), dim3(64), 0, S(stream), p->L, d_alm, \
-                                     p->dmom)
-    if (p->F == 1) GS_DM(1); else if (p->F == 2) GS_DM(2); else GS_DM(3);
-#undef GS_DM
+    with_F(p->F, [&](auto f) {
+        hipLaunchKernelGGL((k_data_moments<decltype(f)::value>), dim3(nblk(p->L + 1, 64)), dim3(64), 0, S(stream), p->L,
+                           d_alm, p->dmom);
+    });
     GS_LAUNCH_CHECK("k_data_moments");
     p->dmom_src = d_alm;
     return 0;
@@ -3396,19 +3451,21 @@ int gs_nc_sweep(gs_plan* p, const double* d_alm, const double* dl, double* s_out
     // native draws: raw moments, the operator applied by the statistics finish
     const bool raw = p->raw_on && z == nullptr;
     if (raw && p->dmom_src != d_alm && data_moments_launch(p, d_alm, stream)) return -1;
-    if (p->par_pending) {
+    if (p->defer.par_pending) {
         // the prologue's parameter table of this step, if this sweep reads it
-        p->par_pending = false;
+        p->defer.par_pending = false;
         if (!(raw && !s_out)) {
-            if (p->par_dl != dl) return set_error("gs_nc_sweep: D_l differs from the prologue's");
+            if (p->defer.par_dl != dl) return set_error("gs_nc_sweep: D_l differs from the prologue's");
             if (gs_block_params(p, GS_MODE_NONCENTERED, dl, p->params, stream)) return -1;
         }
     }
-    if (p->inkernel_params)
-        return sweep_launch(p, d_alm, nullptr, z, seed, it, 0, s_out, p->stats, false, stream, finish != 0,
-                            GS_MODE_NONCENTERED, dl, nullptr, raw);
-    return sweep_launch(p, d_alm, p->params, z, seed, it, 0, s_out, p->stats, false, stream, finish != 0, -1, dl,
-                        nullptr, raw);
+    SweepReq r;
+    r.d_alm = d_alm; r.dl = dl; r.z = z; r.s_out = s_out; r.stats = p->stats;
+    r.seed = seed_words(seed); r.iteration = it;
+    r.raw = raw; r.finish = finish != 0;
+    if (p->inkernel_params) r.op_mode = GS_MODE_NONCENTERED;
+    else r.params = p->params;
+    return sweep_launch(p, r, stream);
 }
 
 int gs_nc_finish(gs_plan* p, void* stream) {
@@ -3419,7 +3476,7 @@ int gs_nc_finish(gs_plan* p, void* stream) {
 int gs_nc_stats(gs_plan* p, double* stats_out, void* stream) {
     if (check_plan(p)) return -1;
     if (!stats_out) return set_error("gs_nc_stats: null argument");
-    if (p->raw_pending) return set_error("gs_nc_stats: the statistics wait for gs_nc_finish");
+    if (p->defer.raw_pending) return set_error("gs_nc_stats: the statistics wait for gs_nc_finish");
     GS_CHECK(hipMemcpyAsync(stats_out, p->stats, sizeof(double) * p->nchains * p->nstat * (p->L + 1),
                             hipMemcpyDeviceToDevice, S(stream)));
     return 0;
@@ -3430,9 +3487,8 @@ int gs_nc_decide(gs_plan* p, double* dl, const double* u_acc, uint64_t seed, uin
     if (check_plan(p)) return -1;
     if (!p->has_mh) return set_error("gs_nc_decide: plan has no MH blocks / proposal variances");
     if (!dl) return set_error("gs_nc_decide: null argument");
-    if (p->pro_pending) return set_error("gs_nc_decide: the prologue's draws wait for gs_nc_finish");
-    const uint32_t slo = (uint32_t)(seed & 0xFFFFFFFFu), shi = (uint32_t)(seed >> 32);
-    return mh_decide(p, p->stats, dl, u_acc, slo, shi, it, accept_out, stream);
+    if (p->defer.pro_pending) return set_error("gs_nc_decide: the prologue's draws wait for gs_nc_finish");
+    return mh_decide(p, p->stats, dl, u_acc, seed_words(seed), it, accept_out, stream);
 }
 
 int gs_nc_decide_fused(gs_plan* p, double* dl, uint64_t seed, uint32_t it, int32_t* accept_out, double* trace,
@@ -3441,10 +3497,10 @@ int gs_nc_decide_fused(gs_plan* p, double* dl, uint64_t seed, uint32_t it, int32
     if (!p->has_mh) return set_error("gs_nc_decide_fused: plan has no MH blocks / proposal variances");
     if (!dl) return set_error("gs_nc_decide_fused: null argument");
     if (trace && capacity < 1) return set_error("gs_nc_decide_fused: capacity < 1");
-    if (p->pro_pending) return set_error("gs_nc_decide_fused: the prologue's draws wait for gs_nc_finish");
-    const uint32_t slo = (uint32_t)(seed & 0xFFFFFFFFu), shi = (uint32_t)(seed >> 32);
+    if (p->defer.pro_pending) return set_error("gs_nc_decide_fused: the prologue's draws wait for gs_nc_finish");
     const MhEpi epi{trace, std::max(capacity, 1), p->adv_counter(), p->nchains, p->graph_adv, nullptr};
-    return mh_decide(p, p->stats, dl, p->u_nat_ready ? p->u_nat : nullptr, slo, shi, it, accept_out, stream, &epi);
+    return mh_decide(p, p->stats, dl, p->defer.u_nat_ready ? p->u_nat : nullptr, seed_words(seed), it, accept_out,
+                     stream, &epi);
 }
 
 int gs_step_noncentered(gs_plan* p, const double* d_alm, double* dl, double* s_out, const double* z,
@@ -3490,19 +3546,19 @@ int gs_step_asis_fused(gs_plan* p, const double* d_alm, double* dl, double* s_ou
     if (trace && capacity < 1) return set_error("gs_step_asis_fused: capacity < 1");
     if (!d_alm || !dl) return set_error("gs_step_asis_fused: null argument");
     double* tmp = dl_tmp_out ? dl_tmp_out : p->dl_tmp;
-    const uint32_t slo = (uint32_t)(seed & 0xFFFFFFFFu), shi = (uint32_t)(seed >> 32);
+    const SeedWords sw = seed_words(seed);
     bool pre = false;
-    if (step_sweep(p, GS_MODE_CENTERED, d_alm, dl, nullptr, seed, it, s_out, stream, true, &pre)) return -1;
+    if (step_sweep(p, GS_MODE_CENTERED, d_alm, dl, nullptr, seed, it, s_out, stream, &pre)) return -1;
     if (cls_draw_launch(p, p->stats, nullptr, seed, it, tmp, nullptr, 1, nullptr, stream, pre ? p->cls_var : nullptr))
         return -1;
     // the non-centred statistics and, in front workgroups of the same launch,
     // the MH proposals from the drawn D_l (tmp); the MH reads tmp and writes dl
     // (no copy: the same values as copying tmp to dl first)
-    if (stats_to_nc_launch(p, tmp, p->stats, stream, true, seed, it)) return -1;
+    if (stats_to_nc_launch(p, tmp, p->stats, stream, true, sw, it)) return -1;
     // the trace record and the counter advance ride in the MH launch (no kernel
     // after it reads the counter: the re-centring uses D_l only)
     const MhEpi epi{trace, trace ? capacity : 1, p->adv_counter(), p->nchains, p->graph_adv, tmp};
-    if (mh_decide(p, p->stats, dl, nullptr, slo, shi, it, accept_out, stream, &epi)) return -1;
+    if (mh_decide(p, p->stats, dl, nullptr, sw, it, accept_out, stream, &epi)) return -1;
     if (recentre && s_out) {
         const bool quirk = (p->quirks & GS_QUIRK_ASIS_RECENTRE_CENTERED) != 0;
         if (gs_recentre(p, dl, quirk ? nullptr : tmp, s_out, stream)) return -1;

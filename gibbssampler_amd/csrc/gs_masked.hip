@@ -38,6 +38,7 @@
 #include "gs_common.h"
 #include "gs_block.h"
 #include "gs_aux.h"
+#include "gs_launch.h"
 
 // library-internal SHT entry points (gs_sht.hip)
 extern "C" long long gs_sht_phi_plane(const gs_sht* p);
@@ -52,6 +53,9 @@ extern "C" int gs_sht_aux_pass_batch(gs_sht* p, int nmap, int ncomp, const doubl
 
 using namespace gs;
 using gs_detail::set_error;
+using gs_detail::with_F;
+using gs_detail::SeedWords;
+using gs_detail::seed_words;
 
 namespace {
 
@@ -1301,12 +1305,10 @@ __global__ void k_mc_params(int L, int nch, const double* __restrict__ dl, const
 
 int mc_params(gs_masked* c, int nch, const double* dl, const double* kap, double* out, hipStream_t st) {
     const dim3 g(nblocks((long long)nch * (c->L + 1), 256)), b(256);
-    if (c->F == 1)
-        hipLaunchKernelGGL(k_mc_params<1>, g, b, 0, st, c->L, nch, dl, c->ell2bin, c->bl, kap[0], kap[1], kap[2], out);
-    else if (c->F == 2)
-        hipLaunchKernelGGL(k_mc_params<2>, g, b, 0, st, c->L, nch, dl, c->ell2bin, c->bl, kap[0], kap[1], kap[2], out);
-    else
-        hipLaunchKernelGGL(k_mc_params<3>, g, b, 0, st, c->L, nch, dl, c->ell2bin, c->bl, kap[0], kap[1], kap[2], out);
+    with_F(c->F, [&](auto f) {
+        hipLaunchKernelGGL(k_mc_params<decltype(f)::value>, g, b, 0, st, c->L, nch, dl, c->ell2bin, c->bl, kap[0],
+                           kap[1], kap[2], out);
+    });
     GS_LAUNCH_CHECK("k_mc_params");
     return 0;
 }
@@ -1363,15 +1365,10 @@ int mc_s_update(gs_masked* c, int over, double* s, const double* zs, long long z
     double imu[3] = {0, 0, 0};
     for (int k = 0; k < c->F; ++k) imu[k] = 1.0 / c->mu[c->rows.r[k]];
     const dim3 g(nblocks(c->nlm, 256), c->B), b(256);
-    if (c->F == 1)
-        hipLaunchKernelGGL(k_mc_s<1>, g, b, 0, st, c->L, c->params, c->r, imu[0], imu[1], imu[2], zs, zss, slo, shi,
-                           chain, sub, it, over, c->alpha, s);
-    else if (c->F == 2)
-        hipLaunchKernelGGL(k_mc_s<2>, g, b, 0, st, c->L, c->params, c->r, imu[0], imu[1], imu[2], zs, zss, slo, shi,
-                           chain, sub, it, over, c->alpha, s);
-    else
-        hipLaunchKernelGGL(k_mc_s<3>, g, b, 0, st, c->L, c->params, c->r, imu[0], imu[1], imu[2], zs, zss, slo, shi,
-                           chain, sub, it, over, c->alpha, s);
+    with_F(c->F, [&](auto f) {
+        hipLaunchKernelGGL(k_mc_s<decltype(f)::value>, g, b, 0, st, c->L, c->params, c->r, imu[0], imu[1], imu[2], zs,
+                           zss, slo, shi, chain, sub, it, over, c->alpha, s);
+    });
     GS_LAUNCH_CHECK("k_mc_s");
     return 0;
 }
@@ -1603,9 +1600,10 @@ static int pcg_apply(gs_masked* c, const double* dl, const double* x, double* ou
     }
     const dim3 g(partial ? nb : nblocks(c->nlm, RED_BLOCK), c->B), b(RED_BLOCK);
     const double iw = 1.0 / c->w;
-    if (c->F == 1) hipLaunchKernelGGL(k_pcg_qdot<1>, g, b, 0, st, c->L, dl, c->bl, x, c->r, iw, out, partial, state);
-    else if (c->F == 2) hipLaunchKernelGGL(k_pcg_qdot<2>, g, b, 0, st, c->L, dl, c->bl, x, c->r, iw, out, partial, state);
-    else hipLaunchKernelGGL(k_pcg_qdot<3>, g, b, 0, st, c->L, dl, c->bl, x, c->r, iw, out, partial, state);
+    with_F(c->F, [&](auto f) {
+        hipLaunchKernelGGL(k_pcg_qdot<decltype(f)::value>, g, b, 0, st, c->L, dl, c->bl, x, c->r, iw, out, partial,
+                           state);
+    });
     GS_LAUNCH_CHECK("k_pcg_qdot");
     return 0;
 }
@@ -1615,23 +1613,19 @@ int gs_masked_pcg_rhs(gs_masked* c, const double* dl, const double* zv, const do
     if (!c) return set_error("null masked context");
     if (!dl || !rhs) return set_error("gs_masked_pcg_rhs: null argument");
     const hipStream_t st = S(stream);
-    const uint32_t slo = (uint32_t)(seed & 0xFFFFFFFFu), shi = (uint32_t)(seed >> 32), ch = (uint32_t)chain;
+    const SeedWords sw = seed_words(seed);
+    const uint32_t ch = (uint32_t)chain;
     hipLaunchKernelGGL(k_pcg_zpix, dim3(nblocks(c->FP, 256), c->B), dim3(256), 0, st, c->npix, c->F, c->rows, c->ninv,
-                       zv, slo, shi, ch, iteration, c->y);
+                       zv, sw.lo, sw.hi, ch, iteration, c->y);
     GS_LAUNCH_CHECK("k_pcg_zpix");
     // adjoint_synthesis_hp: map2alm with healpy's default iter = 3 (utils.py:89,104)
     if (gs_sht_map2alm_batch(c->sht, c->B, c->F, GS_ALM_REAL, c->y, nullptr, c->r, 3, st)) return -1;
     const dim3 g(nblocks(c->nlm, 256), c->B), b(256);
     const double resc = (double)c->npix / (4.0 * PI);
-    if (c->F == 1)
-        hipLaunchKernelGGL(k_pcg_rhs<1>, g, b, 0, st, c->L, dl, c->bl, c->g2, c->r, resc, zs, slo, shi, ch,
-                           iteration, rhs);
-    else if (c->F == 2)
-        hipLaunchKernelGGL(k_pcg_rhs<2>, g, b, 0, st, c->L, dl, c->bl, c->g2, c->r, resc, zs, slo, shi, ch,
-                           iteration, rhs);
-    else
-        hipLaunchKernelGGL(k_pcg_rhs<3>, g, b, 0, st, c->L, dl, c->bl, c->g2, c->r, resc, zs, slo, shi, ch,
-                           iteration, rhs);
+    with_F(c->F, [&](auto f) {
+        hipLaunchKernelGGL(k_pcg_rhs<decltype(f)::value>, g, b, 0, st, c->L, dl, c->bl, c->g2, c->r, resc, zs, sw.lo,
+                           sw.hi, ch, iteration, rhs);
+    });
     GS_LAUNCH_CHECK("k_pcg_rhs");
     return 0;
 }
@@ -1672,10 +1666,10 @@ int gs_masked_pcg_solve(gs_masked* c, const double* dl, const double* rhs, doubl
         GS_CHECK(hipMemcpyAsync(c->pr, rhs, B * n * sizeof(double), hipMemcpyDeviceToDevice, st));
     }
     const dim3 gb(nb, B), bb(RED_BLOCK), g1(1, B);
-#define GS_PI(FF) hipLaunchKernelGGL((k_pcg_init<FF>), gb, bb, 0, st, c->L, c->params_pcg, rhs, c->pr, c->pz, c->pp, \
-                                     c->partial)
-    if (c->F == 1) GS_PI(1); else if (c->F == 2) GS_PI(2); else GS_PI(3);
-#undef GS_PI
+    with_F(c->F, [&](auto f) {
+        hipLaunchKernelGGL(k_pcg_init<decltype(f)::value>, gb, bb, 0, st, c->L, c->params_pcg, rhs, c->pr, c->pz, c->pp,
+                           c->partial);
+    });
     hipLaunchKernelGGL(k_pcg_scal<0>, g1, bb, 0, st, nb, c->partial, dst, tol, maxiter);
     GS_LAUNCH_CHECK("k_pcg_init");
     // the unconverged chains as of the last state read
@@ -1683,10 +1677,10 @@ int gs_masked_pcg_solve(gs_masked* c, const double* dl, const double* rhs, doubl
     const bool compact = B > 1;
     auto iteration = [&]() -> int {
         if (pcg_apply(c, dl, c->pp, c->pq, c->partial, nb, dst, st, na, c->pcg_act)) return -1;
-#define GS_PU(FF) hipLaunchKernelGGL((k_pcg_upd<FF>), gb, bb, 0, st, c->L, nb, c->params_pcg, c->pp, c->pq, x, c->pr, \
-                                     c->pz, c->partial, dst)
-        if (c->F == 1) GS_PU(1); else if (c->F == 2) GS_PU(2); else GS_PU(3);
-#undef GS_PU
+        with_F(c->F, [&](auto f) {
+            hipLaunchKernelGGL(k_pcg_upd<decltype(f)::value>, gb, bb, 0, st, c->L, nb, c->params_pcg, c->pp, c->pq, x,
+                               c->pr, c->pz, c->partial, dst);
+        });
         hipLaunchKernelGGL(k_pcg_scal<2>, g1, bb, 0, st, nb, c->partial, dst, tol, maxiter);
         hipLaunchKernelGGL(k_pcg_dir, gb, bb, 0, st, n, dst, c->pz, c->pp);
         GS_LAUNCH_CHECK("pcg iteration");
@@ -1771,9 +1765,9 @@ int gs_masked_rj_accept(gs_masked* c, const double* dl, const double* rhs, const
     const int nb = (int)std::min<long long>(c->nblk, nblocks(n, RED_BLOCK));
     hipLaunchKernelGGL(k_rj_dot, dim3(nb, c->B), dim3(RED_BLOCK), 0, st, n, rhs, c->pr, s, x, c->partial);
     GS_LAUNCH_CHECK("k_rj_dot");
-    hipLaunchKernelGGL(k_rj_accept, dim3(1, c->B), dim3(RED_BLOCK), 0, st, nb, c->partial, n, um,
-                       (uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32), (uint32_t)chain, iteration, c->accd,
-                       accept, log_ratio);
+    const SeedWords sw = seed_words(seed);
+    hipLaunchKernelGGL(k_rj_accept, dim3(1, c->B), dim3(RED_BLOCK), 0, st, nb, c->partial, n, um, sw.lo, sw.hi,
+                       (uint32_t)chain, iteration, c->accd, accept, log_ratio);
     GS_LAUNCH_CHECK("k_rj_accept");
     hipLaunchKernelGGL(k_select_copy, dim3(nblocks(n, 256), c->B), dim3(256), 0, st, n, c->accd, x, s);
     GS_LAUNCH_CHECK("k_select_copy");
@@ -1803,9 +1797,9 @@ int gs_masked_pcg_work(const gs_masked* c, long long* chain_iterations) {
 static int masked_center(gs_masked* c, int nch, const double* dl, int dir, const double* in, double* out,
                          hipStream_t st) {
     const dim3 g(nblocks(c->NR, 256), nch), b(256);
-    if (c->F == 1) hipLaunchKernelGGL(k_mc_center<1>, g, b, 0, st, c->L, dl, dir, in, out);
-    else if (c->F == 2) hipLaunchKernelGGL(k_mc_center<2>, g, b, 0, st, c->L, dl, dir, in, out);
-    else hipLaunchKernelGGL(k_mc_center<3>, g, b, 0, st, c->L, dl, dir, in, out);
+    with_F(c->F, [&](auto f) {
+        hipLaunchKernelGGL(k_mc_center<decltype(f)::value>, g, b, 0, st, c->L, dl, dir, in, out);
+    });
     GS_LAUNCH_CHECK("k_mc_center");
     return 0;
 }
@@ -2038,19 +2032,20 @@ int gs_masked_tt_fullsky(gs_masked* c, int noncentered, const double* dl, const 
     if (c->F != 1) return set_error("gs_masked_tt_fullsky: temperature-only context required");
     if (!dl || !s_out) return set_error("gs_masked_tt_fullsky: null argument");
     const hipStream_t st = S(stream);
-    const uint32_t slo = (uint32_t)(seed & 0xFFFFFFFFu), shi = (uint32_t)(seed >> 32), ch = (uint32_t)chain;
+    const SeedWords sw = seed_words(seed);
+    const uint32_t ch = (uint32_t)chain;
     hipLaunchKernelGGL(k_pcg_zpix, dim3(nblocks(c->npix, 256), c->B), dim3(256), 0, st, c->npix, 1, c->rows, c->ninv,
-                       zv, slo, shi, ch, iteration, c->y);
+                       zv, sw.lo, sw.hi, ch, iteration, c->y);
     GS_LAUNCH_CHECK("k_pcg_zpix");
     if (gs_sht_map2alm_batch(c->sht, c->B, 1, GS_ALM_REAL, c->y, nullptr, c->r, 3, st)) return -1;
     const double resc = (double)c->npix / (4.0 * PI);
     const double kap = c->ninv0[0] * resc;
     const dim3 g(nblocks(c->nlm, 256), c->B), b(256);
     if (noncentered)
-        hipLaunchKernelGGL(k_tt_fullsky<1>, g, b, 0, st, c->L, dl, c->bl, c->g2, c->r, resc, kap, zs, slo, shi, ch,
+        hipLaunchKernelGGL(k_tt_fullsky<1>, g, b, 0, st, c->L, dl, c->bl, c->g2, c->r, resc, kap, zs, sw.lo, sw.hi, ch,
                            iteration, s_out);
     else
-        hipLaunchKernelGGL(k_tt_fullsky<0>, g, b, 0, st, c->L, dl, c->bl, c->g2, c->r, resc, kap, zs, slo, shi, ch,
+        hipLaunchKernelGGL(k_tt_fullsky<0>, g, b, 0, st, c->L, dl, c->bl, c->g2, c->r, resc, kap, zs, sw.lo, sw.hi, ch,
                            iteration, s_out);
     GS_LAUNCH_CHECK("k_tt_fullsky");
     return 0;
@@ -2065,7 +2060,8 @@ int gs_masked_cr(gs_masked* c, int kind, const double* dl, double* s, double* v,
     if ((kind == GS_MCR_MALA || kind == GS_MCR_AUX_MALA) && c->F != 2)
         return set_error("gs_masked_cr: MALA is defined for the EB model only (CenteredGibbs.py:560-603)");
     const hipStream_t st = S(stream);
-    const uint32_t slo = (uint32_t)(seed & 0xFFFFFFFFu), shi = (uint32_t)(seed >> 32), ch = (uint32_t)chain;
+    const SeedWords sw = seed_words(seed);
+    const uint32_t ch = (uint32_t)chain;
     const long long FP = c->FP, FR = c->FR;
     const int B = c->B;
     double* vv = v ? v : c->vtmp;
@@ -2083,21 +2079,21 @@ int gs_masked_cr(gs_masked* c, int kind, const double* dl, double* s, double* v,
             // (map2alm(v + N^-1 d), :763-765 = :810-812); here that analysis is the
             // one already in c->r (deterministic: the same bits), so each iteration
             // costs one v | s pass and one analysis instead of one and two
-            if (mc_vs(c, 0, s, vv, zv, zvs, slo, shi, ch, SUB_V_INIT, iteration, st)) return -1;
+            if (mc_vs(c, 0, s, vv, zv, zvs, sw.lo, sw.hi, ch, SUB_V_INIT, iteration, st)) return -1;
             for (int k = 0; k < c->n_gibbs; ++k) {
                 const double* zs1 = zs ? zs + (2LL * k) * FR : nullptr;
                 const double* zs2 = zs ? zs + (2LL * k + 1) * FR : nullptr;
                 const double* zvk = zv ? zv + (1LL + k) * FP : nullptr;
-                if (mc_s_update(c, 1, s, zs1, zss, slo, shi, ch, SUB_S + 2 * k, iteration, st)) return -1;
-                if (mc_vs(c, 1, s, vv, zvk, zvs, slo, shi, ch, k, iteration, st)) return -1;
-                if (mc_s_update(c, 1, s, zs2, zss, slo, shi, ch, SUB_S + 2 * k + 1, iteration, st)) return -1;
+                if (mc_s_update(c, 1, s, zs1, zss, sw.lo, sw.hi, ch, SUB_S + 2 * k, iteration, st)) return -1;
+                if (mc_vs(c, 1, s, vv, zvk, zvs, sw.lo, sw.hi, ch, k, iteration, st)) return -1;
+                if (mc_s_update(c, 1, s, zs2, zss, sw.lo, sw.hi, ch, SUB_S + 2 * k + 1, iteration, st)) return -1;
             }
         } else {
             // replay normals per chain: zv [B][n_gibbs][F][Npix], zs [B][n_gibbs][F][NR]
             const long long zvs = (long long)c->n_gibbs * FP, zss = (long long)c->n_gibbs * FR;
             for (int k = 0; k < c->n_gibbs; ++k) {
-                if (mc_vs(c, 0, s, vv, zv ? zv + k * FP : nullptr, zvs, slo, shi, ch, k, iteration, st)) return -1;
-                if (mc_s_update(c, 0, s, zs ? zs + k * FR : nullptr, zss, slo, shi, ch, SUB_S + 2 * k, iteration, st))
+                if (mc_vs(c, 0, s, vv, zv ? zv + k * FP : nullptr, zvs, sw.lo, sw.hi, ch, k, iteration, st)) return -1;
+                if (mc_s_update(c, 0, s, zs ? zs + k * FR : nullptr, zss, sw.lo, sw.hi, ch, SUB_S + 2 * k, iteration, st))
                     return -1;
             }
         }
@@ -2120,14 +2116,14 @@ int gs_masked_cr(gs_masked* c, int kind, const double* dl, double* s, double* v,
     if (mc_gradient_r(c, dl, s, c->grad0, c->r, st)) return -1;
     const uint32_t call = 0;
     hipLaunchKernelGGL(k_mc_propose, dim3(nblocks(c->nlm, 256), B), dim3(256), 0, st, c->L, c->F, c->params_mala, s,
-                       c->grad0, c->tau, zm, slo, shi, ch, (uint32_t)(SUB_MALA + call), iteration, c->snew);
+                       c->grad0, c->tau, zm, sw.lo, sw.hi, ch, (uint32_t)(SUB_MALA + call), iteration, c->snew);
     GS_LAUNCH_CHECK("k_mc_propose");
     if (mc_gradient_r(c, dl, c->snew, c->grad1, c->r1, st)) return -1;
     hipLaunchKernelGGL(k_mc_sums, dim3(c->nblk, B), dim3(RED_BLOCK), 0, st, c->L, c->F, c->npix, dl, c->params_mala,
                        c->tau, s, c->snew, c->grad0, c->grad1, c->g2, c->ninv, nullptr, nullptr, c->partial, c->r,
                        c->r1, c->bl, 1.0 / c->w);
     GS_LAUNCH_CHECK("k_mc_sums");
-    hipLaunchKernelGGL(k_mc_accept, dim3(1, B), dim3(256), 0, st, c->nblk, c->partial, FR, um, slo, shi, ch, call,
+    hipLaunchKernelGGL(k_mc_accept, dim3(1, B), dim3(256), 0, st, c->nblk, c->partial, FR, um, sw.lo, sw.hi, ch, call,
                        iteration, c->accd, accept, log_ratio ? log_ratio : c->lr);
     GS_LAUNCH_CHECK("k_mc_accept");
     hipLaunchKernelGGL(k_select_copy, dim3(nblocks(FR, 256), B), dim3(256), 0, st, FR, c->accd, c->snew, s);
