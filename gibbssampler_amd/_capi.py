@@ -112,6 +112,9 @@ _SIGS = [
     ("gs_nc_stats", ctypes.c_int, [_VP, _VP, _VP]),
     ("gs_nc_decide", ctypes.c_int, [_VP, _VP, _VP, ctypes.c_uint64, ctypes.c_uint32, _VP, _VP]),
     ("gs_nc_decide_fused", ctypes.c_int, [_VP, _VP, ctypes.c_uint64, ctypes.c_uint32, _VP, _VP, ctypes.c_int, _VP]),
+    ("gs_nc_pipe_prepare", ctypes.c_int, [_VP, c_int_p]),
+    ("gs_nc_steps", ctypes.c_int, [_VP, _VP, _VP, ctypes.c_uint64, ctypes.c_int, _VP, ctypes.c_longlong, _VP,
+                                   ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP]),
     ("gs_step_asis", ctypes.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, ctypes.c_uint64, ctypes.c_uint32,
                                     _VP, _VP, ctypes.c_int, _VP]),
     ("gs_iteration_counter", ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_uint32]),

@@ -155,6 +155,12 @@ struct gs_plan {
     //   (par_dl)     the parameter table                   its sweep reads one)
     //   raw_pending  sweep_launch, every call (= raw)      stats_finish; gs_nc_stats refuses to
     //   (raw_dl)                                           run while it is set
+    //
+    // The pipelined schedule (gs_nc_steps) defers nothing through here: it refuses
+    // to start while pro_pending, par_pending or raw_pending is set, launches its
+    // sweeps ahead of the chain (SweepReq::slot: no front workgroups, no
+    // raw_pending) and each step's draws and finish itself; of these members it
+    // writes u_nat_ready and snap_ok alone, as the prologue does for mh_decide.
     struct Deferred {
         // many-chain NC steps: the MH proposals and native accept uniforms depend
         // only on the current D_l and the counters, so they are drawn by extra
@@ -184,6 +190,24 @@ struct gs_plan {
     uint32_t graph_off = 0, graph_adv = 1;
     IterArg ita(uint32_t host_it) const { return IterArg{iter_dev_on ? graph_off : host_it, itp()}; }
     uint32_t* adv_counter() const { return iter_dev_on && graph_adv ? iter_dev : nullptr; }
+    // The pipelined NC schedule (GS_NC_PIPE=0|1, default 1; gs_nc_steps).  A native
+    // raw-moment sweep that stores no map reads the data and the counters only,
+    // not the chain's D_l, so sweep(i+1) runs on a side stream while finish(i)
+    // and mh(i) run on the caller's: only finish -> mh -> finish stays serial.
+    // Step i's sweep fills partial slot i % 2 (slot[0] = partials; slot[1], the
+    // stream and the events exist once gs_nc_pipe_prepare has run).  One side
+    // stream, so sweep(i+1) follows sweep(i): with a stream per slot two sweeps
+    // overlapped each other's tails and the step measured 0.1814 against 0.1600
+    // ms (serial 0.1760; 32 TEB chains at L 1024, profiles/r08_nc_pipeline_ab.jsonl).
+    struct Pipe {
+        bool on = false;             // the option
+        bool ready = false;
+        double* slot[2] = {nullptr, nullptr};
+        hipStream_t side = nullptr;
+        hipEvent_t ev_fork = nullptr;
+        hipEvent_t ev_sweep[2] = {nullptr, nullptr};     // sweep into slot b done
+        hipEvent_t ev_finish[2] = {nullptr, nullptr};    // finish has read slot b
+    } pipe;
     // dominant-kernel timing
     bool timing = false;
     std::vector<hipEvent_t> ev;
@@ -2376,7 +2400,7 @@ __global__ void k_record_trace(long long n, const double* __restrict__ dl, doubl
 // ============================================================================
 // the library options (gs_option_set): a fixed set of names
 static const char* const k_options[] = {
-    "GS_SWEEP_TW", "GS_SWEEP_THROUGHPUT", "GS_NC_RAW", "GS_MH_SPLIT", "GS_CLS_PRE", "GS_CLS_PRE_MANY", "GS_F2_GROUP_BYTES",
+    "GS_SWEEP_TW", "GS_SWEEP_THROUGHPUT", "GS_NC_RAW", "GS_NC_PIPE", "GS_MH_SPLIT", "GS_CLS_PRE", "GS_CLS_PRE_MANY", "GS_F2_GROUP_BYTES",
     "GS_F2_BATCH_BYTES", "GS_SHT_LDS_FFT_MAX", "GS_SHT_SEG", "GS_SHT_SYN", "GS_SHT_ANA", "GS_SHT_MERGE_RINGS",
     "GS_SHT_CONST_RINGS", "GS_SHT_BLOCKS_MFMA", "GS_SHT_BLK_STAGE", "GS_SHT_FUSED_AUX", "GS_SHT_MFMA_MAX_GB",
     "GS_SHT_RING_TW2"};
@@ -2705,6 +2729,10 @@ int gs_plan_create(const gs_model_desc* desc, gs_plan** out) {
         const char* e = gs_detail::option("GS_NC_RAW");
         p->raw_on = e ? std::atoi(e) != 0 : true;
     }
+    {
+        const char* e = gs_detail::option("GS_NC_PIPE");
+        p->pipe.on = e ? std::atoi(e) != 0 : true;
+    }
     const int nraw = F == 3 ? 9 : 2 * F, ndm = F == 3 ? 4 : F;
     rc |= dev_alloc(&p->partials, nc * p->ntile * p->nchunkg * std::max(p->nstat, nraw) * WAVE);
     rc |= dev_alloc(&p->dmom, (size_t)ndm * (L + 1));
@@ -2736,6 +2764,11 @@ int gs_plan_destroy(gs_plan* p) {
                     p->bin2blk, p->mh_lam, p->mh_cnt, p->sd_chain};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
+    if (p->pipe.slot[1]) (void)hipFree(p->pipe.slot[1]);
+    for (hipEvent_t e : {p->pipe.ev_fork, p->pipe.ev_sweep[0], p->pipe.ev_sweep[1], p->pipe.ev_finish[0],
+                         p->pipe.ev_finish[1]})
+        if (e) (void)hipEventDestroy(e);
+    if (p->pipe.side) (void)hipStreamDestroy(p->pipe.side);
     for (hipEvent_t e : p->ev) (void)hipEventDestroy(e);
     delete p;
     return 0;
@@ -2907,27 +2940,34 @@ static ProPre take_pro(gs_plan* p) {
 // rows behind one statistics partial (a sweep workgroup adds its chunks of a tile)
 static int finish_tm(const gs_plan* p) { return p->rows_per_task * (4 / p->sweep_tw); }
 
+// the finish of the raw sums in partials: one workgroup per (chain, tile) sums
+// them and applies the NC operator of dl; pp's draws (seed sw, iteration it)
+// ride in front
+static int finish_raw_launch(gs_plan* p, const double* partials, const double* dl, const ProPre& pp, SeedWords sw,
+                             uint32_t it, double* stats, void* stream) {
+    const long long nr = (long long)p->nchains * p->ntile;
+    const SweepOp op{GS_MODE_NONCENTERED, p->maxbins, dl, p->ell2bin, p->bl, p->kappa[0], p->kappa[1], p->kappa[2]};
+    with_F(p->F, [&](auto f) {
+        hipLaunchKernelGGL((k_stats_finish_raw<decltype(f)::value>), dim3((unsigned)(nr + pp.nbp + pp.nbu)),
+                           dim3(256), 0, S(stream), p->L, p->nchains, p->ntile, p->nchunkg, finish_tm(p), partials,
+                           p->dmom, stats, op, pp.nbp, pp.nbu, pp.u_out, pp.nspec, pp.nacc, pp.n_iter_mh, pp.nbins,
+                           pp.prop_sd, pp.sd_stride, pp.dl, pp.prop, pp.logr, sw.lo, sw.hi, p->ita(it), p->chain0,
+                           pp.snap);
+    });
+    GS_LAUNCH_CHECK("k_stats_finish_raw");
+    return 0;
+}
+
 static int stats_finish(gs_plan* p, double* stats, void* stream) {
     gs_plan::Deferred& d = p->defer;
     const long long n = (long long)p->nchains * p->nstat * p->ntile;
     const int tmf = finish_tm(p);
     if (d.raw_pending) {
-        // raw sums: one workgroup per (chain, tile) sums them and applies the NC
-        // operator of the sweep's D_l; the prologue's deferred draws ride in front
+        // raw sums, the operator of the sweep's D_l; the prologue's deferred draws ride in front
         d.raw_pending = false;
         const bool pro = d.pro_pending;
         const ProPre pp = take_pro(p);
-        const long long nr = (long long)p->nchains * p->ntile;
-        const SweepOp op{GS_MODE_NONCENTERED, p->maxbins, d.raw_dl, p->ell2bin, p->bl, p->kappa[0], p->kappa[1],
-                         p->kappa[2]};
-        with_F(p->F, [&](auto f) {
-            hipLaunchKernelGGL((k_stats_finish_raw<decltype(f)::value>), dim3((unsigned)(nr + pp.nbp + pp.nbu)),
-                               dim3(256), 0, S(stream), p->L, p->nchains, p->ntile, p->nchunkg, tmf, p->partials,
-                               p->dmom, stats, op, pp.nbp, pp.nbu, pp.u_out, pp.nspec, pp.nacc, pp.n_iter_mh, pp.nbins,
-                               pp.prop_sd, pp.sd_stride, pp.dl, pp.prop, pp.logr, d.pro_seed.lo, d.pro_seed.hi,
-                               p->ita(d.pro_it), p->chain0, pp.snap);
-        });
-        GS_LAUNCH_CHECK("k_stats_finish_raw");
+        if (finish_raw_launch(p, p->partials, d.raw_dl, pp, d.pro_seed, d.pro_it, stats, stream)) return -1;
         if (pro) d.snap_ok = true;
         return 0;
     }
@@ -2975,6 +3015,9 @@ struct SweepReq {
     uint32_t iteration = 0, substep = 0;
     // non-null: the C_l draw's variates may ride in this launch (cls_var); set to whether they did
     bool* cls_pre_done = nullptr;
+    // >= 0: a sweep ahead of the chain into partial slot `slot` (gs_nc_steps): raw,
+    // no map, no finish, no front workgroups, nothing left pending in Deferred
+    int slot = -1;
 };
 
 static int sweep_launch(gs_plan* p, const SweepReq& r, void* stream) {
@@ -2983,8 +3026,14 @@ static int sweep_launch(gs_plan* p, const SweepReq& r, void* stream) {
     if (!r.d_alm || !r.stats || (!r.given && !r.params && r.op_mode < 0 && !raw_nost) || (r.given && !r.s_out) ||
         ((r.op_mode >= 0 || r.raw) && !r.dl) || (r.raw && (r.given || r.z)))
         return set_error("gs_cr_sweep: null argument");
-    p->defer.raw_pending = r.raw;
-    p->defer.raw_dl = r.raw ? r.dl : nullptr;
+    const bool ahead = r.slot >= 0;
+    if (ahead && (r.slot > 1 || !p->pipe.ready || !raw_nost || r.finish || r.cls_pre_done))
+        return set_error("gs_cr_sweep: a sweep ahead is a raw-moment sweep alone, into a prepared slot");
+    double* const partials = ahead ? p->pipe.slot[r.slot] : p->partials;
+    if (!ahead) {
+        p->defer.raw_pending = r.raw;
+        p->defer.raw_dl = r.raw ? r.dl : nullptr;
+    }
     const SweepOp op{r.op_mode, p->maxbins, r.dl, p->ell2bin, p->bl, p->kappa[0], p->kappa[1], p->kappa[2]};
     const int nlog = (int)((long long)p->nchains * p->npair);
     dim3 g((unsigned)nlog), b(256);
@@ -3006,7 +3055,7 @@ static int sweep_launch(gs_plan* p, const SweepReq& r, void* stream) {
         }
     } else {
         // the prologue's deferred MH draws in front of this sweep (native, same step)
-        if (p->defer.pro_pending && !rep && !r.given && r.iteration == p->defer.pro_it) {
+        if (!ahead && p->defer.pro_pending && !rep && !r.given && r.iteration == p->defer.pro_it) {
             pp = take_pro(p);
             p->defer.snap_ok = true;
         }
@@ -3022,7 +3071,7 @@ static int sweep_launch(gs_plan* p, const SweepReq& r, void* stream) {
     const SweepKernel k =
         with_F(p->F, [&](auto f) { return sweep_variant<decltype(f)::value>(lat, r.given, rep, r.raw, st); });
     hipLaunchKernelGGL(k, g, b, 0, S(stream), p->L, p->nchains, p->ntile, p->nchunkg, p->rows_per_task, p->sweep_tw,
-                       p->tasks, r.d_alm, r.params, r.z, r.s_out, p->partials, r.seed.lo, r.seed.hi,
+                       p->tasks, r.d_alm, r.params, r.z, r.s_out, partials, r.seed.lo, r.seed.hi,
                        p->ita(r.iteration), r.substep, p->chain0, op, cp, pp, nlog);
     GS_LAUNCH_CHECK("k_cr_sweep");
     if (p->timing && record_ev(e1, S(stream))) return -1;
@@ -3501,6 +3550,119 @@ int gs_nc_decide_fused(gs_plan* p, double* dl, uint64_t seed, uint32_t it, int32
     const MhEpi epi{trace, std::max(capacity, 1), p->adv_counter(), p->nchains, p->graph_adv, nullptr};
     return mh_decide(p, p->stats, dl, p->defer.u_nat_ready ? p->u_nat : nullptr, seed_words(seed), it, accept_out,
                      stream, &epi);
+}
+
+int gs_nc_pipe_prepare(gs_plan* p, int* on) {
+    if (check_plan(p)) return -1;
+    if (!on) return set_error("gs_nc_pipe_prepare: null argument");
+    gs_plan::Pipe& q = p->pipe;
+    *on = 0;
+    if (!q.on || !p->raw_on || !p->has_mh) return 0;
+    if (!q.ready) {
+        const int nraw = p->F == 3 ? 9 : 2 * p->F;
+        if (dev_alloc(&q.slot[1], (size_t)p->nchains * p->ntile * p->nchunkg * std::max(p->nstat, nraw) * WAVE))
+            return -1;
+        q.slot[0] = p->partials;
+        GS_CHECK(hipStreamCreateWithFlags(&q.side, hipStreamNonBlocking));
+        for (int b = 0; b < 2; ++b) {
+            GS_CHECK(hipEventCreateWithFlags(&q.ev_sweep[b], hipEventDisableTiming));
+            GS_CHECK(hipEventCreateWithFlags(&q.ev_finish[b], hipEventDisableTiming));
+        }
+        GS_CHECK(hipEventCreateWithFlags(&q.ev_fork, hipEventDisableTiming));
+        q.ready = true;
+    }
+    *on = 1;
+    return 0;
+}
+
+// K native NC steps, pipelined.  Launch order and event edges (M the caller's
+// stream, S the side stream; step i uses slot i % 2):
+//
+//   M   fork ---------- draws+finish(0) - mh(0) - draws+finish(1) - mh(1) - draws+finish(2) ...
+//   S     `- sweep(0) -'- sweep(1) --------------'- sweep(2) ----------------'
+//                                                  (after finish(0))
+//
+//   sweep(i)  follows sweep(i-1) on S and waits for finish(i-2), the last reader
+//             of its slot; ev_sweep[i % 2]
+//   finish(i) waits for sweep(i) and, by M's order, for mh(i-1) (+ adaptation),
+//             whose D_l, scales and accept uniforms it reads or overwrites;
+//             ev_finish[i % 2]
+// Every sweep is followed on M by a wait for its event, so S has joined M when
+// the last step is emitted (a capture of M closes).
+// K = 1: nothing overlaps and the sweep stays on M.
+int gs_nc_steps(gs_plan* p, const double* d_alm, double* dl, uint64_t seed, int nsteps, int32_t* accept,
+                long long accept_stride, double* trace, int capacity, int adapt, int time_every, void* stream) {
+    if (check_plan(p)) return -1;
+    gs_plan::Pipe& q = p->pipe;
+    gs_plan::Deferred& d = p->defer;
+    if (!q.ready) return set_error("gs_nc_steps: the pipeline is not prepared (gs_nc_pipe_prepare)");
+    if (!p->iter_dev_on) return set_error("gs_nc_steps: device iteration counter not enabled");
+    if (!d_alm || !dl || !accept) return set_error("gs_nc_steps: null argument");
+    if (nsteps < 1 || accept_stride < 0 || time_every < 0) return set_error("gs_nc_steps: argument out of range");
+    if (trace && capacity < 1) return set_error("gs_nc_steps: capacity < 1");
+    if (adapt && !p->adapt_on) return set_error("gs_nc_steps: adaptation not enabled (gs_mh_adapt_enable)");
+    if (d.pro_pending || d.par_pending || d.raw_pending)
+        return set_error("gs_nc_steps: an earlier step's draws or statistics still wait for their launch");
+    const SeedWords sw = seed_words(seed);
+    const hipStream_t M = S(stream);
+    if (p->dmom_src != d_alm && data_moments_launch(p, d_alm, stream)) return -1;
+    const bool fork = nsteps > 1;
+    int nsweep = 0;                  // sweeps emitted so far
+    const auto sweep_ahead = [&](int i) -> int {
+        const int b = i & 1;
+        const hipStream_t s = fork ? q.side : M;
+        if (fork && i >= 2) GS_CHECK(hipStreamWaitEvent(s, q.ev_finish[b], 0));
+        p->graph_off = (uint32_t)i;
+        p->graph_adv = 0;
+        if (time_every > 0) p->timing = i % time_every == 0;     // the event pair goes on the sweep's own branch
+        SweepReq r;
+        r.d_alm = d_alm; r.dl = dl; r.stats = p->stats; r.seed = sw;
+        r.raw = true; r.finish = false; r.slot = b;
+        if (p->inkernel_params) r.op_mode = GS_MODE_NONCENTERED;
+        else r.params = p->params;
+        if (sweep_launch(p, r, s)) return -1;
+        if (fork) GS_CHECK(hipEventRecord(q.ev_sweep[b], s));
+        ++nsweep;
+        return 0;
+    };
+    const auto emit = [&]() -> int {
+        if (fork) {
+            GS_CHECK(hipEventRecord(q.ev_fork, M));
+            GS_CHECK(hipStreamWaitEvent(q.side, q.ev_fork, 0));
+        }
+        if (sweep_ahead(0)) return -1;
+        for (int i = 0; i < nsteps; ++i) {
+            const int b = i & 1;
+            const bool last = i == nsteps - 1;
+            if (!last && sweep_ahead(i + 1)) return -1;
+            if (fork) GS_CHECK(hipStreamWaitEvent(M, q.ev_sweep[b], 0));
+            // the kernels read base + offset; the base moves once, in the last step's
+            // decide, which every sweep of this call precedes (through its finish)
+            if (last && nsweep != nsteps) return set_error("gs_nc_steps: a sweep would follow the counter advance");
+            p->graph_off = (uint32_t)i;
+            p->graph_adv = last ? (uint32_t)nsteps : 0u;
+            // the step's MH draws: <= 4 chains in a prologue launch, else in front of the finish
+            ProPre pp{};
+            if (p->nchains <= 4) {
+                if (gs_nc_prologue(p, dl, nullptr, seed, 0, stream)) return -1;
+            } else {
+                d.u_nat_ready = p->nacc > 0;
+                pp = pro_front(p, dl, true, d.u_nat_ready);
+            }
+            if (finish_raw_launch(p, q.slot[b], dl, pp, sw, 0, p->stats, stream)) return -1;
+            d.snap_ok = true;
+            if (fork && i + 2 < nsteps) GS_CHECK(hipEventRecord(q.ev_finish[b], M));
+            int32_t* const acc = accept + (long long)i * accept_stride;
+            const MhEpi epi{trace, std::max(capacity, 1), p->adv_counter(), p->nchains, p->graph_adv, nullptr};
+            if (mh_decide(p, p->stats, dl, d.u_nat_ready ? p->u_nat : nullptr, sw, 0, acc, stream, &epi)) return -1;
+            if (adapt && gs_mh_adapt(p, acc, stream)) return -1;
+        }
+        return 0;
+    };
+    const int rc = emit();
+    p->graph_off = 0;                // back to one step per replay
+    p->graph_adv = 1;
+    return rc;
 }
 
 int gs_step_noncentered(gs_plan* p, const double* d_alm, double* dl, double* s_out, const double* z,

@@ -330,6 +330,21 @@ class GibbsPlan:
         C.check(self.lib.gs_nc_decide_fused(self._h, C.ptr(dl), int(seed), int(iteration), C.ptr(accept),
                                             C.ptr(trace), int(capacity), self._s()), "gs_nc_decide_fused")
 
+    def nc_pipe_prepare(self):
+        """Whether multi-step native NC graphs pipeline (gs_nc_pipe_prepare; option
+        GS_NC_PIPE); the first call allocates: not inside a capture."""
+        on = ctypes.c_int()
+        C.check(self.lib.gs_nc_pipe_prepare(self._h, ctypes.byref(on)), "gs_nc_pipe_prepare")
+        return bool(on.value)
+
+    def nc_steps(self, d, dl, nsteps, seed=0, accept=None, accept_stride=0, trace=None, capacity=0, adapt=False,
+                 time_every=0):
+        """nsteps pipelined native NC steps without a stored map (gs_nc_steps):
+        step i writes its flags to accept[i * accept_stride ...] (elements)."""
+        C.check(self.lib.gs_nc_steps(self._h, C.ptr(d), C.ptr(dl), int(seed), int(nsteps), C.ptr(accept),
+                                     int(accept_stride), C.ptr(trace), int(capacity), 1 if adapt else 0,
+                                     int(time_every), self._s()), "gs_nc_steps")
+
     def step_asis(self, d, dl, s_out, z=None, igvar=None, u_prop=None, u_acc=None, seed=0, iteration=0,
                   accept=None, dl_tmp=None, recentre=False):
         C.check(self.lib.gs_step_asis(self._h, C.ptr(d), C.ptr(dl), C.ptr(s_out), C.ptr(z), C.ptr(igvar),

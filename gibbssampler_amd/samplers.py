@@ -289,18 +289,31 @@ class BatchedRunner:
         replay = nsteps steps).  time_sweeps: bracket the CR-sweep kernel of every
         ``time_every``-th step by event-record nodes (plan.sweep_timing), so the
         sweep's duration is measured on its own stream inside the replay (an event
-        node costs ~5 us of the step); collect with plan.sweep_timing(False)."""
+        node costs ~5 us of the step); collect with plan.sweep_timing(False).
+        NC steps without a stored map are emitted pipelined by the library
+        (plan.nc_steps; option GS_NC_PIPE): a timed sweep then shares the GPU with
+        the previous step's finish and MH, and its time includes that."""
         if self.rng != "native":
             raise ValueError("capture_steps: native RNG runs only")
         p = self.plan
         p.iteration_counter(True, self.iteration + 1)
+        # NC without a stored map: the sweeps do not depend on the chains' state, and
+        # the library emits the steps pipelined (sweep i + 1 beside finish and MH of
+        # step i, gs_nc_steps); a stored map, ASIS and centered keep the serial order
+        pipe = self.kind == "noncentered" and self.s is None and \
+            (accept_trace is None or accept_trace[0].is_contiguous()) and p.nc_pipe_prepare()
         torch.cuda.synchronize()
         if time_sweeps:
             p.sweep_timing(True)
         g = torch.cuda.CUDAGraph()
         try:
             with _capture(g):
-                for i in range(nsteps):
+                if pipe:
+                    acc = self.accept if accept_trace is None else accept_trace
+                    p.nc_steps(self.d, self.dl, nsteps, seed=self.seed, accept=acc,
+                               accept_stride=0 if accept_trace is None else accept_trace.stride(0), trace=trace,
+                               capacity=trace_capacity or 0, adapt=adapt, time_every=time_every if time_sweeps else 0)
+                for i in range(0 if pipe else nsteps):
                     # step i reads base + i; only the last step's last launch advances
                     # the base (by nsteps): one counter ticket per replay
                     p.graph_step(i, nsteps if i == nsteps - 1 else 0)
@@ -331,6 +344,7 @@ class BatchedRunner:
             p.graph_step(0, 1)
         self.graph = g
         self.graph_steps = nsteps
+        self.graph_pipelined = bool(pipe)
         return g
 
     def _launch_step(self, it, z=None, ig=None, up=None, ua=None):

@@ -99,6 +99,8 @@ const char* gs_last_error(void);
  *   GS_SWEEP_TW          1 | 2 | 4  CR-sweep workgroup shape (tiles x chunks;
  *                                   2 suits --skymap store, 1 the default)
  *   GS_SWEEP_THROUGHPUT  1          few-chain plans use the throughput form
+ *   GS_NC_RAW            0 | 1      raw-moment statistics of native NC sweeps
+ *   GS_NC_PIPE           0 | 1      pipelined multi-step NC graphs (gs_nc_steps)
  *   GS_MH_SPLIT          0 | 1      NC MH in one / two workgroups per chain
  *   GS_CLS_PRE, GS_CLS_PRE_MANY  0 | 1  C_l-draw variates inside the sweep
  *   GS_F2_GROUP_BYTES, GS_F2_BATCH_BYTES  f2 workspace budgets (bytes)
@@ -244,6 +246,30 @@ int gs_nc_decide(gs_plan* plan, double* dl_binned, const double* u_accept_replay
  * workgroup read it at its start). */
 int gs_nc_decide_fused(gs_plan* plan, double* dl_binned, uint64_t seed, uint32_t iteration, int32_t* accept_out,
                        double* trace, int capacity, void* stream);
+/* The pipelined NC schedule (native RNG, raw-moment statistics, no stored map;
+ * option GS_NC_PIPE=0 at plan creation turns it off).  Such a sweep reads the
+ * data and the counters only, never the chain's D_l, so the sweep of step i + 1
+ * runs while the statistics finish and the MH of step i run; only finish -> MH
+ * -> finish stays serial.
+ * gs_nc_pipe_prepare sets *on to whether the plan pipelines and, the first time
+ * it does, allocates a second buffer of statistic partials, a side stream and
+ * the fork / join events: call it outside a stream capture.
+ * gs_nc_steps emits nsteps whole steps on `stream` and the plan's side stream
+ * (joined back into `stream` before it returns: capturable into one hipGraph).
+ * It needs the device iteration counter: step i reads base + i, and the last
+ * step's decide launch advances the base by nsteps after every sweep has read
+ * it; gs_graph_step is back at (0, 1) afterwards.  Step i writes its accept
+ * flags to accept + i * accept_stride (stride 0: one buffer), records D_l in
+ * trace (nullable) as gs_nc_decide_fused does and, with adapt != 0, runs
+ * gs_mh_adapt on its flags before the next step's proposals.  time_every > 0:
+ * the sweep of every time_every-th step is bracketed for gs_sweep_timing on the
+ * side stream that runs it (the time includes sharing the GPU with the previous
+ * step's finish and MH); 0 leaves the timing state alone.  The results are those
+ * of nsteps times gs_nc_prologue, gs_nc_sweep, gs_nc_decide_fused, bit for bit. */
+int gs_nc_pipe_prepare(gs_plan* plan, int* on);
+int gs_nc_steps(gs_plan* plan, const double* d_alm, double* dl_binned, uint64_t seed, int nsteps,
+                int32_t* accept_out, long long accept_stride, double* trace, int capacity, int adapt,
+                int time_every, void* stream);
 /* dl_tmp_out: nullable, receives the centered draw; recentre: 0 lazy (s_out keeps the
  * centered CR draw), 1 materialise the re-centred map in s_out */
 int gs_step_asis(gs_plan* plan, const double* d_alm, double* dl_binned, double* s_out,
