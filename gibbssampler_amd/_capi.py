@@ -122,6 +122,11 @@ _SIGS = [
     ("gs_advance_iteration", ctypes.c_int, [_VP, _VP]),
     ("gs_record_trace", ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int, ctypes.c_uint32, _VP]),
     ("gs_sweep_timing", ctypes.c_int, [_VP, ctypes.c_int, c_double_p, c_int_p]),
+    ("gs_summary_bytes", ctypes.c_int, [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_longlong)]),
+    ("gs_summary_reset", ctypes.c_int, [_VP] + [ctypes.c_int] * 5 + [_VP]),
+    ("gs_summary_update", ctypes.c_int, [_VP] + [ctypes.c_int] * 5 + [_VP, ctypes.c_int, ctypes.c_uint32, ctypes.c_int,
+                                                                       _VP, ctypes.c_longlong, _VP]),
+    ("gs_summary_finish", ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [_VP] * 6),
     ("gs_sht_create", ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(_VP)]),
     ("gs_sht_destroy", ctypes.c_int, [_VP]),
     ("gs_sht_info", ctypes.c_int, [_VP, c_int_p, c_int_p, ctypes.POINTER(ctypes.c_longlong),

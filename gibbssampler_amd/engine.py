@@ -378,6 +378,85 @@ class GibbsPlan:
         return tot.value, n.value
 
 
+class SummaryState:
+    """Streaming posterior summary of D_l chains over the gs_summary_* C-ABI
+    (gs_summary.hip documents the state layout and the formulas): a flat fp64
+    device tensor ``data`` = 8 header doubles (int64 sample count first), the
+    per-series fields [6 + 3 max_lag, nchains, nspec * maxbins] and the int64
+    accept counts [nchains, nacc].  Plan-independent: any trace tensor
+    [capacity, nchains, nspec, maxbins] can be summarised."""
+    HDR = 8
+    POOLED = ("mean", "var", "min", "max", "ess", "ess_truncated", "rhat")
+
+    def __init__(self, nchains, nspec, maxbins, nacc, max_lag, device=None, data=None):
+        _require_gpu()
+        self.lib = C.load()
+        self.nchains, self.nspec, self.maxbins = int(nchains), int(nspec), int(maxbins)
+        self.nacc, self.max_lag = int(nacc), int(max_lag)
+        nb = ctypes.c_longlong()
+        C.check(self.lib.gs_summary_bytes(*self._dims(), ctypes.byref(nb)), "gs_summary_bytes")
+        self.nfields = 6 + 3 * self.max_lag
+        self.ns = self.nchains * self.nspec * self.maxbins
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+        if data is None:
+            self.data = torch.zeros(nb.value // 8, dtype=torch.float64, device=dev)
+        else:
+            self.data = torch.as_tensor(data, dtype=torch.float64).to(dev).contiguous().clone()
+            if self.data.numel() * 8 != nb.value:
+                raise ValueError("summary state: size does not match its dimensions")
+
+    def _dims(self):
+        return self.nchains, self.nspec, self.maxbins, self.nacc, self.max_lag
+
+    def reset(self):
+        C.check(self.lib.gs_summary_reset(C.ptr(self.data), *self._dims(), C.stream_ptr()), "gs_summary_reset")
+
+    def update(self, trace, capacity, first_iteration, nsteps, accept=None, accept_stride=0):
+        """Add iterations first_iteration .. first_iteration + nsteps - 1 from the
+        trace ring (iteration it in slot (it - 1) % capacity) and, with accept
+        (int32, step i at accept + i * accept_stride elements), their flags."""
+        if trace.numel() < int(capacity) * self.ns:
+            raise ValueError("summary update: the trace is smaller than capacity rows")
+        if accept is not None and accept.numel() < (int(nsteps) - 1) * int(accept_stride) + self.nchains * self.nacc:
+            raise ValueError("summary update: the accept trace is smaller than nsteps steps")
+        C.check(self.lib.gs_summary_update(C.ptr(self.data), *self._dims(), C.ptr(trace), int(capacity),
+                                           int(first_iteration), int(nsteps), C.ptr(accept), int(accept_stride),
+                                           C.stream_ptr()), "gs_summary_update")
+
+    @property
+    def n(self):
+        """Samples summarised (reads the device count: synchronises)."""
+        return int(self.data[:1].view(torch.int64).item())
+
+    def fields(self):
+        """The per-series fields as a view [6 + 3 max_lag, nchains, nspec * maxbins]."""
+        return self.data[self.HDR:self.HDR + self.nfields * self.ns].view(self.nfields, self.nchains, -1)
+
+    def accept_counts(self):
+        """int64 [nchains, nacc] (a view of the state)."""
+        return self.data[self.HDR + self.nfields * self.ns:].view(torch.int64).view(self.nchains, self.nacc)
+
+    def finish(self, gather=None):
+        """Run the finish; device tensors: the POOLED names [nspec, maxbins],
+        chain_mean / chain_var [C, nspec, maxbins], acf [max_lag + 1, nspec,
+        maxbins], gamma [C, max_lag + 1, nspec, maxbins] and n.  gather
+        (ShardContext.gather): the fields are all-gathered along the chain axis
+        first and the finish runs over every rank's chains."""
+        data, nch = self.data, self.nchains
+        if gather is not None:
+            body = gather(self.fields().contiguous(), dim=1)
+            nch = int(body.shape[1])
+            data = torch.cat([self.data[:self.HDR], body.reshape(-1)])
+        K, dev = self.max_lag, self.data.device
+        z = lambda *shape: torch.zeros(*shape, self.nspec, self.maxbins, dtype=torch.float64, device=dev)
+        pooled, cm, cv, acf, gamma = z(7), z(nch), z(nch), z(K + 1), z(nch, K + 1)
+        C.check(self.lib.gs_summary_finish(C.ptr(data), nch, self.nspec, self.maxbins, K, C.ptr(pooled), C.ptr(cm),
+                                           C.ptr(cv), C.ptr(acf), C.ptr(gamma), C.stream_ptr()), "gs_summary_finish")
+        out = {k: pooled[i] for i, k in enumerate(self.POOLED)}
+        out.update(chain_mean=cm, chain_var=cv, acf=acf, gamma=gamma, n=self.n)
+        return out
+
+
 def stats_layout(F):
     """Names of the statistic rows (include/gibbs_capi.h GS_NSTAT_*)."""
     return {1: ["ssTT", "dTsT"], 2: ["ssEE", "ssBB", "dEsE", "dBsB"],

@@ -38,7 +38,11 @@ job-script.sh:6-8), ``dist_backend`` ("nccl" = RCCL, or "gloo"),
 ``keep_skymap`` (full-sky runs: keep each iteration's CR map on the device
 for the ``skymap`` property; off by default -- the reference's ``run`` returns
 D_l and accept histories only, and without the map store the CR sweep is ~20 %
-faster).
+faster), ``summary`` (True or {max_lag, start}: a streaming posterior summary
+of the D_l chains kept on the device -- mean, variance, autocorrelation, ESS
+and R-hat over all chains, the ``posterior_summary`` property) and
+``keep_history`` (False with a summary: no history is allocated and ``run``
+returns None for the histories and accepts); full-sky harmonic runs only.
 """
 import os
 import time
@@ -146,8 +150,13 @@ class GibbsSampler:
                  gibbs_cr=False, rj_step=False, ula=False, *, nchains=1, rng="native", seed=0, fields=None,
                  chain0=0, reference_quirks=True, noise_pol=None, proposal_variances=None,
                  metropolis_blocks=None, n_iter_metropolis=1, mask_path=None, distributed=False,
-                 dist_backend=None, keep_skymap=False, sht_mode="auto"):
+                 dist_backend=None, keep_skymap=False, sht_mode="auto", summary=None, keep_history=True):
         self.shard = None
+        # streaming posterior summary (samplers.BatchedRunner.run(summary=, keep_history=))
+        from .samplers import check_summary
+        check_summary(summary, keep_history)
+        self.summary = summary if summary else None
+        self.keep_history = bool(keep_history)
         # masked / pixel-TT runs: the Legendre stage of their transforms ("auto":
         # matrix-core tables from 4 chains on small maps, else the recurrence;
         # "recurrence"; "mfma").  Chain b of a batch equals a one-chain run of
@@ -318,6 +327,8 @@ class GibbsSampler:
         resume, self._resume_state = getattr(self, "_resume_state", None), None
         init = dls_init if isinstance(dls_init, dict) or resume is not None else {self.spectra[0]: dls_init}
         kw = {"n_warmup": self.n_warmup, "target_accept": self.target_accept} if self.n_warmup else {}
+        if self.summary is not None:
+            kw.update(summary=self.summary, keep_history=self.keep_history)
         first = runner.iteration if resume is None else int(resume["iteration"])
         h, acc, t = runner.run(init, self.n_iter, timings=True,
                                gather=self.shard.gather if self.shard is not None else None, resume=resume, **kw)
@@ -328,6 +339,16 @@ class GibbsSampler:
             self._mean_accept_by_block = {
                 s: (v[k0:].reshape(-1, v.shape[2] // nm, nm).mean(axis=(0, 2)) if v.shape[0] > k0 else
                     np.full(v.shape[2] // nm, np.nan)) for s, v in acc.items()}
+        if h is None:
+            # keep_history=False: the acceptance per block from the summary's counts
+            # (over its summarised iterations: the post warm-up ones by default)
+            cnt, n = runner.summary_accept_counts()
+            if cnt is not None:
+                nm = self.n_iter_metropolis
+                self._mean_accept_by_block = {
+                    s: (v.reshape(-1, v.shape[1] // nm, nm).sum(axis=(0, 2)) / (n * v.shape[0] * nm) if n > 0 else
+                        np.full(v.shape[1] // nm, np.nan)) for s, v in cnt.items()}
+            return None, None, t
         h = {s: self._squeeze(v) for s, v in h.items()}
         if acc is not None:
             acc = {s: self._squeeze(v) for s, v in acc.items()}
@@ -372,6 +393,21 @@ class GibbsSampler:
             raise NotImplementedError("n_warmup > 0: masked and TT-pixel runs use the pixel-domain Metropolis step "
                                       "(one shared proposal table); the warm-up adaptation covers the full-sky "
                                       "harmonic (all_sph) samplers only")
+
+    def _check_summary(self):
+        if self.summary is not None and (self.mask is not None or getattr(self, "tt_pixel", False)):
+            raise NotImplementedError("summary: masked and TT-pixel runs keep their histories on the host; the "
+                                      "streaming summary covers the full-sky harmonic (all_sph) samplers only")
+
+    @property
+    def posterior_summary(self):
+        """After a run with summary=: per spectrum a dict of numpy arrays -- mean,
+        var, min, max, ess, ess_truncated, rhat [nbins], chain_mean, chain_var
+        [chains, nbins], acf [max_lag + 1, nbins] -- and n, the samples per
+        chain; over every rank's chains when distributed."""
+        if self._runner is None:
+            raise RuntimeError("posterior_summary: nothing has run yet")
+        return self._runner.summary(self.shard.gather if self.shard is not None else None)
 
     @property
     def tuned_proposal_variances(self):
@@ -419,6 +455,7 @@ class CenteredGibbs(GibbsSampler):
         self.overrelaxation = overrelaxation
         self.cr_ula = ula
         self.tt_pixel = self._tt_pixel_path(all_sph)
+        self._check_summary()
         if self.tt_pixel:
             from .tt import TTCenteredConstrainedRealization, TTCenteredClsSampler
             m = self._tt_model(False)
@@ -450,14 +487,14 @@ class CenteredGibbs(GibbsSampler):
             return self._run_masked(dls_init)
         h, _, t = self._run_common(dls_init)
         n = len(t)
-        return h, np.ones(n, dtype=int), np.asarray(t), np.zeros(n)
+        return h, np.ones(n, dtype=int), np.asarray(t), np.zeros(n)     # h is None with keep_history=False
 
     def run_temperature(self, dls_init):
         """GibbsSampler.run_temperature (GibbsSampler.py:76-116)."""
         if self.tt_pixel:
             return self._tt.run_centered(dls_init, self.n_iter)
         h, _, t = self._run_common(dls_init)
-        return h["TT"], np.ones(len(t), dtype=int), list(t)
+        return None if h is None else h["TT"], np.ones(len(t), dtype=int), list(t)
 
 
 class NonCenteredGibbs(GibbsSampler):
@@ -474,6 +511,7 @@ class NonCenteredGibbs(GibbsSampler):
         self.all_sph = all_sph
         self.tt_pixel = self._tt_pixel_path(all_sph)
         self._set_warmup(n_warmup, target_accept)
+        self._check_summary()
         if self.tt_pixel:
             from .tt import TTNonCenteredConstrainedRealization, TTNonCenteredClsSampler
             m = self._tt_model(True)
@@ -502,6 +540,8 @@ class NonCenteredGibbs(GibbsSampler):
         if self.tt_pixel:
             return self._tt.run_noncentered(dls_init, self.n_iter)
         h, acc, t = self._run_common(dls_init)
+        if h is None:
+            return None, None, np.asarray(t)
         return h["TT"][1:], acc["TT"], np.asarray(t)
 
 
@@ -523,6 +563,7 @@ class ASIS(GibbsSampler):
         self.overrelaxation = overrelaxation
         self.tt_pixel = self._tt_pixel_path(all_sph)
         self._set_warmup(n_warmup, target_accept)
+        self._check_summary()
         if self.tt_pixel:
             from .tt import TTCenteredConstrainedRealization, TTCenteredClsSampler, TTNonCenteredClsSampler
             m = self._tt_model(True)
@@ -560,6 +601,8 @@ class ASIS(GibbsSampler):
         if self.tt_pixel:
             return self._tt.run_asis(dls_init, self.n_iter, gibbs_cr=self.gibbs_cr)
         h, acc, t = self._run_common(dls_init)
+        if h is None:
+            return None, None, np.ones(len(t), dtype=int), np.asarray(t)
         return h["TT"], acc["TT"], np.ones(len(t), dtype=int), np.asarray(t)
 
 

@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from . import _capi as C
-from .engine import GibbsPlan, MH_ORDER
+from .engine import GibbsPlan, MH_ORDER, SummaryState
 
 INIT_ITER = 0xFFFFFFFF
 ADAPT_KAPPA = 0.6       # Robbins-Monro step n^-kappa of the warm-up adaptation
@@ -45,6 +45,26 @@ def check_warmup(kind, rng, n_warmup, target_accept=0.25):
         if not 0.0 < float(target_accept) < 1.0:
             raise ValueError("target_accept must lie in (0, 1)")
     return n_warmup
+
+
+def check_summary(summary, keep_history=True):
+    """run(summary=...): None / False (off), True, or {max_lag: 32, start: None};
+    returns None or (max_lag, start)."""
+    if summary is None or summary is False:
+        if not keep_history:
+            raise ValueError("keep_history=False needs summary= (nothing else would be kept of the run)")
+        return None
+    opts = {} if summary is True else dict(summary)
+    bad = set(opts) - {"max_lag", "start"}
+    if bad:
+        raise ValueError(f"summary: unknown options {sorted(bad)}")
+    max_lag = int(opts.get("max_lag", 32))
+    if not 0 <= max_lag <= 64:
+        raise ValueError("summary: max_lag must lie in [0, 64]")
+    start = opts.get("start")
+    if start is not None and int(start) < 0:
+        raise ValueError("summary: start must be >= 0")
+    return max_lag, None if start is None else int(start)
 
 
 def warmup_of_state(st):
@@ -122,6 +142,10 @@ class BatchedRunner:
         self.n_warmup = 0
         self.target_accept = 0.25
         self._gather = None
+        # streaming summary of the D_l chains (run(summary=...)): the device state
+        # and the iteration after which it summarises
+        self._summary = None
+        self.summary_start = 0
 
     def __del__(self):
         # dropped inside another sampler's capture: keep the kept hipGraphs, the
@@ -182,6 +206,9 @@ class BatchedRunner:
             lam, cnt = p.mh_scale_get()
             st.update(mh_log_scale=lam.cpu(), mh_count=cnt.cpu(), mh_n_warmup=int(self.n_warmup),
                       mh_target_accept=float(self.target_accept))
+        if self._summary is not None:
+            st.update(summary_state=self._summary.data.cpu().clone(), summary_max_lag=self._summary.max_lag,
+                      summary_start=int(self.summary_start))
         if self.rng == "replay":
             name, keys, pos, has_gauss, cached = np.random.get_state()
             st.update(numpy_rng_keys=torch.from_numpy(np.asarray(keys, dtype=np.int64)), numpy_rng_pos=int(pos),
@@ -221,6 +248,12 @@ class BatchedRunner:
         # a state without scales (older checkpoints) is "not adapting": no warm-up
         # is left, and the plan's proposal table stays as it is
         self.n_warmup = nw
+        # a state without a summary (older checkpoints included) is "no summary"
+        if st.get("summary_state") is not None:
+            self._summary_alloc(int(st["summary_max_lag"]), data=st["summary_state"])
+            self.summary_start = int(st["summary_start"])
+        else:
+            self._summary = None
         if self.rng == "replay" and "numpy_rng_keys" in st:
             np.random.set_state(("MT19937", st["numpy_rng_keys"].numpy().astype(np.uint32), st["numpy_rng_pos"],
                                  st["numpy_rng_has_gauss"], st["numpy_rng_cached"]))
@@ -282,6 +315,72 @@ class BatchedRunner:
             lam = gather(lam, dim=0)
         return tuned_variances(p.proposal_variances, p.blocks, p.bins, p.mh_block_layout(),
                                lam.mean(dim=0).cpu().numpy())
+
+    # -- streaming summary ---------------------------------------------------------------
+    def _summary_alloc(self, max_lag, data=None):
+        """The summary state for max_lag (kept across runs of the same max_lag and
+        zeroed; replaced otherwise), or the restored state `data`."""
+        p, sm = self.plan, self._summary
+        if data is not None:
+            self._summary = SummaryState(p.nchains, p.nspec, p.maxbins, max(p.nacc, 1), max_lag, device=p.device,
+                                         data=data)
+        elif sm is not None and sm.max_lag == max_lag:
+            sm.reset()
+        else:
+            self._summary = SummaryState(p.nchains, p.nspec, p.maxbins, max(p.nacc, 1), max_lag, device=p.device)
+
+    def _summary_update(self, trace, capacity, it0, k, acc=None, acc_stride=0):
+        """Summarise iterations it0 + 1 .. it0 + k (in the trace ring; step i's
+        flags at acc[i]) except those up to summary_start."""
+        first = max(it0, self.summary_start) + 1
+        n = it0 + k - first + 1
+        if n <= 0:
+            return
+        if acc is not None and self.kind != "centered":
+            acc = acc[first - it0 - 1:] if acc_stride else acc
+        else:
+            acc = None
+        self._summary.update(trace, capacity, first, n, accept=acc, accept_stride=acc_stride)
+
+    def summary(self, gather=None):
+        """The posterior summary of the last run(summary=...): per spectrum a dict
+        of numpy arrays -- mean, var, min, max, ess, ess_truncated, rhat [nbins],
+        chain_mean, chain_var [chains, nbins], acf [max_lag + 1, nbins] -- and
+        n, the samples per chain.  gather (ShardContext.gather; default: the
+        gather of the last run()): the per-chain state is all-gathered along the
+        chain axis and the statistics are over every rank's chains."""
+        if self._summary is None:
+            raise RuntimeError("summary: the last run() kept no summary (run(summary=True))")
+        p = self.plan
+        out = self._summary.finish(gather if gather is not None else self._gather)
+        n = out.pop("n")
+        out.pop("gamma")
+        host = {k: v.cpu().numpy() for k, v in out.items()}
+        res = {}
+        for i, s in enumerate(p.spectra):
+            nb = len(p.bins[s]) - 1
+            res[s] = {k: v[..., i, :nb].copy() for k, v in host.items()}
+            res[s]["ess_truncated"] = res[s]["ess_truncated"] != 0
+            res[s]["n"] = n
+        return res
+
+    def summary_accept_counts(self, gather=None):
+        """(counts per spectrum {s: int64 [chains, flags]}, n) of the summarised
+        iterations (None for the centered sampler)."""
+        if self._summary is None or self.kind == "centered":
+            return None, 0
+        p = self.plan
+        cnt = self._summary.accept_counts()
+        gather = gather if gather is not None else self._gather
+        if gather is not None:
+            cnt = gather(cnt.contiguous(), dim=0)
+        cnt = cnt.cpu().numpy()
+        out, off = {}, 0
+        for s in MH_ORDER[p.F]:
+            n = (len(p.blocks[s]) - 1) * p.n_iter_metropolis
+            out[s] = cnt[:, off:off + n]
+            off += n
+        return out, self._summary.n
 
     def capture_steps(self, nsteps, trace=None, trace_capacity=None, time_sweeps=False, time_every=1,
                       accept_trace=None, adapt=False):
@@ -373,7 +472,7 @@ class BatchedRunner:
 
     # -- a whole run --------------------------------------------------------------------
     def run(self, dls_init, n_iter, timings=False, gather=None, graph_chunk=32, resume=None, n_warmup=0,
-            target_accept=0.25):
+            target_accept=0.25, summary=None, keep_history=True):
         """n_iter iterations from dls_init; returns (histories, accepts[, step
         times]).  gather: ShardContext.gather of a torchrun job -- the device
         histories of every rank are all-gathered along the chain axis (global
@@ -386,9 +485,19 @@ class BatchedRunner:
         for the rest, an ordinary MH chain.  The histories keep their shape
         (warm-up rows included); runner.n_warmup is the iteration the warm-up
         ends at.  A resumed state carries its own warm-up bookkeeping and goes
-        on with it; n_warmup > 0 with a resume adds that many warm-up iterations."""
+        on with it; n_warmup > 0 with a resume adds that many warm-up iterations.
+        summary: None, True or {max_lag: 32, start: None} -- a streaming summary
+        of the D_l chains (moments, autocovariances up to max_lag, ESS, R-hat;
+        runner.summary()) updated on the device from the trace ring after every
+        chunk replay (eager / replay-RNG steps: after every step).  Iterations up
+        to `start` (default: the iteration the warm-up ends at) and the initial
+        row are not summarised.  A resumed state that carries a summary continues
+        it; a run without resume starts a new one.  keep_history=False (needs a
+        summary): no history is allocated on the device or the host and the
+        histories and accepts are returned as None."""
         p = self.plan
         n_warmup = check_warmup(self.kind, self.rng, n_warmup, target_accept)
+        sm_opts = check_summary(summary, keep_history)
         self._gather = gather
         if resume is not None:
             self.load_state_dict(resume)
@@ -402,13 +511,25 @@ class BatchedRunner:
                 self._adapt_enable(target_accept)
                 p.mh_scale_set(torch.zeros(p.nchains, p.nblocks_mh, dtype=torch.float64),
                                torch.zeros(p.nchains, p.nblocks_mh, dtype=torch.int32))
+        if resume is None or self._summary is None:
+            # a new summary (a resumed state that carries one continues it instead)
+            if sm_opts is None:
+                self._summary = None
+            else:
+                self._summary_alloc(sm_opts[0])
+                self.summary_start = self.n_warmup if sm_opts[1] is None else sm_opts[1]
+        sm = self._summary
+        if sm is None and not keep_history:
+            raise ValueError("keep_history=False needs a summary")
         # steps of this run that adapt; warm-up and frozen steps never share a graph
         n_adapt = min(max(self.n_warmup - self.iteration, 0), n_iter)
         with_start = self.kind != "asis"
-        H = p.zeros(n_iter + (1 if with_start else 0), p.nchains, p.nspec, p.maxbins)
-        A = p.zeros(n_iter, p.nchains, max(p.nacc, 1), dtype=torch.int32)
-        if with_start:
-            H[0].copy_(self.dl)
+        H = A = None
+        if keep_history:
+            H = p.zeros(n_iter + (1 if with_start else 0), p.nchains, p.nspec, p.maxbins)
+            A = p.zeros(n_iter, p.nchains, max(p.nacc, 1), dtype=torch.int32)
+            if with_start:
+                H[0].copy_(self.dl)
         t_steps = []
         if self.rng == "native" and graph_chunk and n_iter > 0:
             # the iterations as replays of captured hipGraphs of `chunk` steps
@@ -429,7 +550,7 @@ class BatchedRunner:
             # single-rank runs: each finished chunk of the histories goes to pinned
             # host memory on a copy stream while the next chunk computes (only the
             # last chunk's transfer is left after the loop)
-            if gather is None:
+            if gather is None and keep_history:
                 Hh = torch.empty(H.shape, dtype=H.dtype, pin_memory=True)
                 Ah = torch.empty(A.shape, dtype=A.dtype, pin_memory=True)
                 cs = cache.setdefault("copy_stream", torch.cuda.Stream())
@@ -451,13 +572,18 @@ class BatchedRunner:
                 cache[key].replay()
                 self.iteration += k
                 e1.record()
+                if sm is not None:
+                    # one launch on the run's stream: the chunk's rows of the ring
+                    # and its accept flags (the captured graphs are not touched)
+                    self._summary_update(trace, chunk, self.iteration - k, k, acc_tr, acc_tr.stride(0))
                 h0, h1 = (0 if done == 0 else off + done), off + done + k
-                if r0 == 0:
-                    H[off + done:h1].copy_(trace[:k])
-                else:
-                    H[off + done:h1].copy_(trace[(torch.arange(k) + r0) % chunk])
-                A[done:done + k].copy_(acc_tr[:k])
-                if gather is None:
+                if keep_history:
+                    if r0 == 0:
+                        H[off + done:h1].copy_(trace[:k])
+                    else:
+                        H[off + done:h1].copy_(trace[(torch.arange(k) + r0) % chunk])
+                    A[done:done + k].copy_(acc_tr[:k])
+                if gather is None and keep_history:
                     ev = torch.cuda.Event()
                     ev.record()
                     cs.wait_event(ev)
@@ -474,7 +600,7 @@ class BatchedRunner:
             self.graph = None
             p.iteration_counter(False)
             n_iter = 0
-            if gather is None:
+            if gather is None and keep_history:
                 cs.synchronize()
                 H, A = Hh, Ah
         for i in range(n_iter):
@@ -482,12 +608,21 @@ class BatchedRunner:
             self.step()
             if i < n_adapt:
                 p.mh_adapt(self.accept)
-            H[i + (1 if with_start else 0)].copy_(self.dl)
-            if self.kind != "centered":
-                A[i].copy_(self.accept)
+            if sm is not None:
+                # the chain's D_l as a one-row trace
+                self._summary_update(self.dl, 1, self.iteration - 1, 1, self.accept, 0)
+            if keep_history:
+                H[i + (1 if with_start else 0)].copy_(self.dl)
+                if self.kind != "centered":
+                    A[i].copy_(self.accept)
             if timings:
                 torch.cuda.synchronize()
                 t_steps.append(time.perf_counter() - t0)
+        if not keep_history:
+            if timings:
+                torch.cuda.synchronize()
+                return None, None, np.array(t_steps)
+            return None, None
         if gather is not None:
             H = gather(H, dim=1)
             if self.kind != "centered":

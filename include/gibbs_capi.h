@@ -294,6 +294,45 @@ int gs_advance_iteration(gs_plan* plan, void* stream);
 int gs_record_trace(gs_plan* plan, const double* dl_binned, double* trace, int capacity, uint32_t iteration,
                     void* stream);
 
+/* ---- streaming posterior summaries of the D_l chains (gs_summary.hip) ----------
+ * Plan-independent: they summarise any trace tensor [capacity][nchains][nspec]
+ * [maxbins] (fp64; the layout of gs_record_trace and of the fused steps' trace
+ * ring).  A series is one (chain, spectrum, bin); the state is a caller-owned
+ * DEVICE buffer of gs_summary_bytes bytes (8-byte aligned) holding, per series
+ * in fp64, the first sample r, the Welford mean and M2, min, max, S = sum y_t
+ * with y_t = x_t - r, the lag products P_j = sum_{t > j} y_t y_{t-j} for
+ * j = 1..max_lag (0 <= max_lag <= 64) and the first and last max_lag values of
+ * y, then int64 accept counts [nchains][nacc]; one int64 sample count n for
+ * the whole state (gs_summary.hip documents the layout and every formula).
+ * gs_summary_reset zeroes the state.
+ * gs_summary_update adds the nsteps consecutive iterations first_iteration,
+ * first_iteration + 1, ... (iteration it lies in slot (it - 1) % capacity;
+ * nsteps <= capacity, first_iteration >= 1) in one launch, in iteration order
+ * per series: the state's bits do not depend on how the iterations were cut
+ * into launches.  accept_trace (nullable): int32 flags, step i of this call at
+ * accept_trace + i * accept_stride, [nchains][nacc]; they are added into the
+ * counts.  Successive updates of one state must be ordered on one stream.
+ * gs_summary_finish, one thread per (spectrum, bin) over the C chains of a
+ * state (C need not be a plan's chain count: a state whose per-series fields
+ * were all-gathered along the chain axis is summarised over every rank's
+ * chains).  Outputs, DEVICE fp64 with nsb = nspec * maxbins fastest:
+ *   pooled     [7][nsb]  mean, variance, min, max, ess, ess_truncated (0 / 1), rhat
+ *   chain_mean [C][nsb], chain_var [C][nsb]
+ *   acf        [max_lag + 1][nsb]  the multi-chain autocorrelation rho_j
+ *   gamma      [C][max_lag + 1][nsb]  per-chain autocovariances (divisor n)
+ * rhat is Gelman-Rubin's sqrt(var+ / W); ess = C n / tau with Geyer's initial
+ * monotone positive sequence over the pairs rho_2k + rho_2k+1 up to max_lag,
+ * ess_truncated = 1 when no negative pair ended the sum (ess is then an upper
+ * estimate).  W == 0: rhat, ess and rho are NaN; C == 1: rhat is NaN; n <= j:
+ * gamma_j is NaN. */
+int gs_summary_bytes(int nchains, int nspec, int maxbins, int nacc, int max_lag, long long* bytes /* HOST */);
+int gs_summary_reset(void* state, int nchains, int nspec, int maxbins, int nacc, int max_lag, void* stream);
+int gs_summary_update(void* state, int nchains, int nspec, int maxbins, int nacc, int max_lag, const double* trace,
+                      int capacity, uint32_t first_iteration, int nsteps, const int32_t* accept_trace,
+                      long long accept_stride, void* stream);
+int gs_summary_finish(const void* state, int C, int nspec, int maxbins, int max_lag, double* pooled,
+                      double* chain_mean, double* chain_var, double* acf, double* gamma, void* stream);
+
 /* device-side timing of the dominant kernel: with enable = 1 every later CR-sweep
  * launch is bracketed by hipEvents on its stream (also while the stream is
  * captured into a hipGraph: external event-record nodes, timed at each replay);
