@@ -90,6 +90,7 @@ _SIGS = [
                                    _VP, _VP, _VP]),
     ("gs_sweep_stats", ctypes.c_int, [_VP, _VP, _VP, _VP, _VP]),
     ("gs_cls_draw", ctypes.c_int, [_VP, _VP, _VP, ctypes.c_uint64, ctypes.c_uint32, _VP, _VP]),
+    ("gs_cls_scale_trace", ctypes.c_int, [_VP, _VP, ctypes.c_int, _VP]),
     ("gs_nc_mh", ctypes.c_int, [_VP, _VP, _VP, _VP, _VP, ctypes.c_uint64, ctypes.c_uint32, _VP, _VP]),
     ("gs_mh_adapt_enable", ctypes.c_int, [_VP, ctypes.c_double, ctypes.c_double]),
     ("gs_mh_adapt", ctypes.c_int, [_VP, _VP, _VP]),
@@ -127,6 +128,11 @@ _SIGS = [
     ("gs_summary_update", ctypes.c_int, [_VP] + [ctypes.c_int] * 5 + [_VP, ctypes.c_int, ctypes.c_uint32, ctypes.c_int,
                                                                        _VP, ctypes.c_longlong, _VP]),
     ("gs_summary_finish", ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [_VP] * 6),
+    ("gs_br_bytes", ctypes.c_int, [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_longlong)]),
+    ("gs_br_reset", ctypes.c_int, [_VP] + [ctypes.c_int] * 4 + [_VP]),
+    ("gs_br_update", ctypes.c_int, [_VP] + [ctypes.c_int] * 4 + [_VP, _VP, ctypes.c_uint32, _VP, ctypes.c_int,
+                                                                 ctypes.c_uint32, ctypes.c_int, _VP]),
+    ("gs_br_finish", ctypes.c_int, [_VP] + [ctypes.c_int] * 4 + [_VP] * 5),
     ("gs_sht_create", ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(_VP)]),
     ("gs_sht_destroy", ctypes.c_int, [_VP]),
     ("gs_sht_info", ctypes.c_int, [_VP, c_int_p, c_int_p, ctypes.POINTER(ctypes.c_longlong),

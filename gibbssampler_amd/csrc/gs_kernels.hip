@@ -139,6 +139,10 @@ struct gs_plan {
     bool cls_pre = false;
     bool cls_pre_many = false;       // the same for many chains: front workgroups of the throughput sweep
     double* cls_var = nullptr;       // [nchains][nspec][maxbins][3]
+    // the caller's scale trace ring (gs_cls_scale_trace; not owned): every C_l
+    // draw of the plan records its conditional's scale there; nullptr: none
+    double* scale_tr = nullptr;      // [scale_cap][nchains][nspec][maxbins]
+    int scale_cap = 1;
     // Work that one call of a step leaves to a later call of the same step:
     //
     //   member       set by                                consumed by
@@ -982,11 +986,18 @@ __device__ __forceinline__ void cls_draw_body(int chain, int sp, int b, int L, i
                                               const double* __restrict__ variates, uint32_t seed_lo, uint32_t seed_hi,
                                               uint32_t iter, int chain0, double* __restrict__ dl_out,
                                               double* __restrict__ trace, int cap, int nchains,
-                                              const double* __restrict__ pre = nullptr) {
+                                              const double* __restrict__ pre = nullptr,
+                                              double* __restrict__ scales = nullptr, int scap = 1) {
     constexpr int NSP = F == 1 ? 1 : (F == 2 ? 2 : 4);
     constexpr int NS = SweepAcc<F>::NS;
     const int Lp1 = L + 1;
     const int nb = nbins_arr[sp];
+    // scale trace (gs_cls_scale_trace), laid out and slotted as the D_l trace:
+    // the scale of the conditional this draw samples -- beta of an inverse-Gamma
+    // spectrum, (a, dd, c) = Psi of the TEB block in the TT, EE and TE slots --
+    // and 0 for the bins that are not drawn
+    double* sc = scales ? scales + ((long long)((iter + (uint32_t)scap - 1u) % (uint32_t)scap) * nchains + chain) * NSP * maxbins
+                        : nullptr;
     // trace slot of this iteration: trace[(iter - 1) % cap][chain][nspec][maxbins]
     double* tr = trace ? trace + ((long long)((iter + (uint32_t)cap - 1u) % (uint32_t)cap) * nchains + chain) * NSP * maxbins
                        : nullptr;
@@ -1004,6 +1015,7 @@ __device__ __forceinline__ void cls_draw_body(int chain, int sp, int b, int L, i
             if (tr) { tr[0 * maxbins + b] = dl_out[((long long)chain * NSP + 0) * maxbins + b];
                       tr[1 * maxbins + b] = dl_out[((long long)chain * NSP + 1) * maxbins + b];
                       tr[3 * maxbins + b] = dl_out[((long long)chain * NSP + 3) * maxbins + b]; }
+            if (sc) { sc[0 * maxbins + b] = 0.0; sc[1 * maxbins + b] = 0.0; sc[3 * maxbins + b] = 0.0; }
             return;
         }
         {
@@ -1070,12 +1082,18 @@ __device__ __forceinline__ void cls_draw_body(int chain, int sp, int b, int L, i
             dl_out[((long long)chain * NSP + 1) * maxbins + b] = ee;
             dl_out[((long long)chain * NSP + 3) * maxbins + b] = te;
             if (tr) { tr[0 * maxbins + b] = tt; tr[1 * maxbins + b] = ee; tr[3 * maxbins + b] = te; }
+            if (sc) {
+                sc[0 * maxbins + b] = b < 2 ? 0.0 : a;
+                sc[1 * maxbins + b] = b < 2 ? 0.0 : dd;
+                sc[3 * maxbins + b] = b < 2 ? 0.0 : c;
+            }
         }
         return;
     }
     if (b >= maxbins) return;
     if (b >= nb) {
         if (tr) tr[sp * maxbins + b] = out[b];
+        if (sc) sc[sp * maxbins + b] = 0.0;
         return;
     }
     {
@@ -1107,6 +1125,7 @@ __device__ __forceinline__ void cls_draw_body(int chain, int sp, int b, int L, i
         }
         out[b] = b < 2 ? 0.0 : beta * X;
         if (tr) tr[sp * maxbins + b] = out[b];
+        if (sc) sc[sp * maxbins + b] = b < 2 ? 0.0 : beta;
     }
 }
 
@@ -1117,11 +1136,12 @@ __global__ __launch_bounds__(64) void k_cls_draw(int L, int nchains, int maxbins
                                                  uint32_t seed_hi, IterArg itarg, int chain0,
                                                  double* __restrict__ dl_out, double* __restrict__ trace, int cap,
                                                  uint32_t* __restrict__ counter, uint32_t adv,
-                                                 const double* __restrict__ pre) {
+                                                 const double* __restrict__ pre, double* __restrict__ scales,
+                                                 int scap) {
     const uint32_t iter = itarg.get();
     cls_draw_body<F>(blockIdx.x, blockIdx.y, blockIdx.z * blockDim.x + threadIdx.x, L, maxbins, bins, nbins_arr,
                      stats, variates, seed_lo, seed_hi, iter, chain0, dl_out, trace,
-                     cap, nchains, pre);
+                     cap, nchains, pre, scales, scap);
     if (counter) ticket_advance(counter, gridDim.x * gridDim.y * gridDim.z, adv);
 }
 
@@ -3102,9 +3122,23 @@ static int cls_draw_launch(gs_plan* p, const double* stats, const double* variat
     with_F(p->F, [&](auto f) {
         hipLaunchKernelGGL((k_cls_draw<decltype(f)::value>), g, b, 0, S(stream), p->L, p->nchains, p->maxbins, p->bins,
                            p->meta, stats, variates, sw.lo, sw.hi, p->ita(iteration), p->chain0, dl_out, trace, cap,
-                           counter, p->graph_adv, pre);
+                           counter, p->graph_adv, pre, p->scale_tr, p->scale_cap);
     });
     GS_LAUNCH_CHECK("k_cls_draw");
+    return 0;
+}
+
+int gs_cls_scale_trace(gs_plan* p, double* scales, int capacity, void* stream) {
+    if (check_plan(p)) return -1;
+    if (scales && capacity < 1) return set_error("gs_cls_scale_trace: capacity < 1");
+    // a graph captured from here on would hold the pointer as a kernel argument
+    // while the graphs captured so far hold the old one: the caller changes it
+    // between captures, never inside one (the NULL stream cannot be captured)
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (stream && (hipStreamIsCapturing(S(stream), &cs) != hipSuccess || cs != hipStreamCaptureStatusNone))
+        return set_error("gs_cls_scale_trace: the stream is being captured (attach or detach outside a capture)");
+    p->scale_tr = scales;
+    p->scale_cap = scales ? capacity : 1;
     return 0;
 }
 

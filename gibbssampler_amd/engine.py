@@ -100,6 +100,7 @@ class GibbsPlan:
             a[0] = 1
             self._alphas[s] = a
         self.adapting = False
+        self.scale_trace = None         # the attached scale ring (cls_scale_trace)
         self._acc_layout = []
         if self.blocks is not None:
             for s in MH_ORDER[self.F]:
@@ -203,6 +204,16 @@ class GibbsPlan:
         C.check(self.lib.gs_cls_draw(self._h, C.ptr(stats), C.ptr(variates), int(seed), int(iteration),
                                      C.ptr(out), self._s()), "gs_cls_draw")
         return out
+
+    def cls_scale_trace(self, scales, capacity=1):
+        """Attach the scale trace ring [capacity, nchains, nspec, maxbins] every
+        C_l draw of the plan records its conditional's scale in (slot
+        (iteration - 1) % capacity), or detach it (scales None).  Refused while
+        the current stream is being captured (gs_cls_scale_trace)."""
+        if scales is not None and scales.numel() < int(capacity) * self.nchains * self.nspec * self.maxbins:
+            raise ValueError("cls_scale_trace: the ring is smaller than capacity rows")
+        C.check(self.lib.gs_cls_scale_trace(self._h, C.ptr(scales), int(capacity), self._s()), "gs_cls_scale_trace")
+        self.scale_trace = scales
 
     def mh_propose(self, dl, u_prop=None, seed=0, iteration=0, with_uniforms=False):
         """(prop, logr[, native accept uniforms]) of the NC MH step (no decisions)."""
@@ -455,6 +466,104 @@ class SummaryState:
         out = {k: pooled[i] for i, k in enumerate(self.POOLED)}
         out.update(chain_mean=cm, chain_var=cv, acf=acf, gamma=gamma, n=self.n)
         return out
+
+
+def br_shapes(nfields, bins, maxbins=None):
+    """The shape table of the centered conditionals (gs_br.hip): (alpha [nspec,
+    maxbins], half_mask).  With n_b = l1^2 - l0^2: alpha = n_b / 2 - 1 for the
+    inverse-Gamma spectra; n_b / 2 - 2 for TT and EE of the TEB block, whose
+    recorded scale Psi_ii is twice the conditional's (half_mask bits); NaN for
+    TE, bins 0 and 1 and the bins past a spectrum's count."""
+    spectra = SPECTRA[int(nfields)]
+    nb = [len(bins[s]) - 1 for s in spectra]
+    maxbins = max(nb) if maxbins is None else int(maxbins)
+    alpha = np.full((len(spectra), maxbins), np.nan)
+    half = 0
+    for k, s in enumerate(spectra):
+        if nfields == 3 and s == "TE":
+            continue
+        b = np.asarray(bins[s], dtype=np.float64)
+        n_b = b[1:] ** 2 - b[:-1] ** 2
+        iw = nfields == 3 and s in ("TT", "EE")
+        alpha[k, :nb[k]] = 0.5 * n_b - (2.0 if iw else 1.0)
+        alpha[k, :2] = np.nan
+        half |= (1 << k) if iw else 0
+    return alpha, half
+
+
+class BlackwellRaoState:
+    """Streaming Blackwell-Rao marginal posteriors over the gs_br_* C-ABI
+    (gs_br.hip documents the state and the order of operations): a flat fp64
+    device tensor ``data`` = 8 header doubles (int64 iteration count first), the
+    planes m and S [2, nchains, nspec * maxbins * G] and the int64 counts of
+    skipped rows [nchains, nspec].  grid [nspec, maxbins, G] and alpha [nspec,
+    maxbins] (br_shapes) are kept on the device.  Plan-independent: any scale
+    ring [capacity, nchains, nspec, maxbins] can be accumulated."""
+    HDR = 8
+
+    def __init__(self, nchains, grid, alpha, half_mask=0, device=None, data=None):
+        _require_gpu()
+        self.lib = C.load()
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+        self.grid = torch.as_tensor(grid, dtype=torch.float64).to(dev).contiguous()
+        self.alpha = torch.as_tensor(alpha, dtype=torch.float64).to(dev).contiguous()
+        if self.grid.dim() != 3 or tuple(self.alpha.shape) != tuple(self.grid.shape[:2]):
+            raise ValueError("Blackwell-Rao state: grid must be [nspec, maxbins, G] and alpha [nspec, maxbins]")
+        self.nchains, self.half_mask = int(nchains), int(half_mask)
+        self.nspec, self.maxbins, self.G = (int(v) for v in self.grid.shape)
+        nb = ctypes.c_longlong()
+        C.check(self.lib.gs_br_bytes(*self._dims(), ctypes.byref(nb)), "gs_br_bytes")
+        self.ne = self.nchains * self.nspec * self.maxbins * self.G
+        if data is None:
+            self.data = torch.zeros(nb.value // 8, dtype=torch.float64, device=dev)
+        else:
+            self.data = torch.as_tensor(data, dtype=torch.float64).to(dev).contiguous().clone()
+            if self.data.numel() * 8 != nb.value:
+                raise ValueError("Blackwell-Rao state: size does not match its dimensions")
+
+    def _dims(self):
+        return self.nchains, self.nspec, self.maxbins, self.G
+
+    def reset(self):
+        C.check(self.lib.gs_br_reset(C.ptr(self.data), *self._dims(), C.stream_ptr()), "gs_br_reset")
+
+    def update(self, scales, capacity, first_iteration, nsteps):
+        """Add iterations first_iteration .. first_iteration + nsteps - 1 from the
+        scale ring (iteration it in slot (it - 1) % capacity)."""
+        if scales.numel() < int(capacity) * self.nchains * self.nspec * self.maxbins:
+            raise ValueError("Blackwell-Rao update: the scale ring is smaller than capacity rows")
+        C.check(self.lib.gs_br_update(C.ptr(self.data), *self._dims(), C.ptr(self.grid), C.ptr(self.alpha),
+                                      self.half_mask, C.ptr(scales), int(capacity), int(first_iteration), int(nsteps),
+                                      C.stream_ptr()), "gs_br_update")
+
+    @property
+    def n(self):
+        """Iterations added (reads the device count: synchronises)."""
+        return int(self.data[:1].view(torch.int64).item())
+
+    def fields(self):
+        """The planes m and S as a view [2, nchains, nspec * maxbins * G]."""
+        return self.data[self.HDR:self.HDR + 2 * self.ne].view(2, self.nchains, -1)
+
+    def bad(self):
+        """int64 [nchains, nspec]: rows skipped for a scale <= 0 or not finite (a view)."""
+        return self.data[self.HDR + 2 * self.ne:].view(torch.int64).view(self.nchains, self.nspec)
+
+    def finish(self, gather=None):
+        """Device tensors logpdf [nspec, maxbins, G] and mass [nspec, maxbins], and
+        n.  gather (ShardContext.gather): the planes are all-gathered along the
+        chain axis first and the finish runs over every rank's chains."""
+        data, nch = self.data, self.nchains
+        if gather is not None:
+            body = gather(self.fields().contiguous(), dim=1)
+            nch = int(body.shape[1])
+            data = torch.cat([self.data[:self.HDR], body.reshape(-1)])
+        dev = self.data.device
+        logpdf = torch.zeros(self.nspec, self.maxbins, self.G, dtype=torch.float64, device=dev)
+        mass = torch.zeros(self.nspec, self.maxbins, dtype=torch.float64, device=dev)
+        C.check(self.lib.gs_br_finish(C.ptr(data), nch, self.nspec, self.maxbins, self.G, C.ptr(self.grid),
+                                      C.ptr(self.alpha), C.ptr(logpdf), C.ptr(mass), C.stream_ptr()), "gs_br_finish")
+        return {"logpdf": logpdf, "mass": mass, "n": self.n}
 
 
 def stats_layout(F):

@@ -43,6 +43,11 @@ of the D_l chains kept on the device -- mean, variance, autocorrelation, ESS
 and R-hat over all chains, the ``posterior_summary`` property) and
 ``keep_history`` (False with a summary: no history is allocated and ``run``
 returns None for the histories and accepts); full-sky harmonic runs only.
+``blackwell_rao`` ({"points": G, "span": (lo, hi)} or {"grid": array}: the
+streaming Blackwell-Rao marginal posterior of every drawn bin on a grid, the
+``blackwell_rao_posterior`` property; it too allows ``keep_history=False``)
+and ``keep_scales`` (keep the scale history of the centered conditionals, the
+``h_scales`` property): full-sky CenteredGibbs and ASIS only.
 """
 import os
 import time
@@ -150,13 +155,18 @@ class GibbsSampler:
                  gibbs_cr=False, rj_step=False, ula=False, *, nchains=1, rng="native", seed=0, fields=None,
                  chain0=0, reference_quirks=True, noise_pol=None, proposal_variances=None,
                  metropolis_blocks=None, n_iter_metropolis=1, mask_path=None, distributed=False,
-                 dist_backend=None, keep_skymap=False, sht_mode="auto", summary=None, keep_history=True):
+                 dist_backend=None, keep_skymap=False, sht_mode="auto", summary=None, keep_history=True,
+                 blackwell_rao=None, keep_scales=False):
         self.shard = None
         # streaming posterior summary (samplers.BatchedRunner.run(summary=, keep_history=))
         from .samplers import check_summary
-        check_summary(summary, keep_history)
+        check_summary(summary, keep_history or bool(blackwell_rao))
         self.summary = summary if summary else None
         self.keep_history = bool(keep_history)
+        # streaming Blackwell-Rao posteriors and the scale history
+        # (samplers.BatchedRunner.run(blackwell_rao=, keep_scales=)); checked once the bins are known
+        self.blackwell_rao = blackwell_rao if blackwell_rao else None
+        self.keep_scales = bool(keep_scales)
         # masked / pixel-TT runs: the Legendre stage of their transforms ("auto":
         # matrix-core tables from 4 chains on small maps, else the recurrence;
         # "recurrence"; "mfma").  Chain b of a batch equals a one-chain run of
@@ -199,6 +209,8 @@ class GibbsSampler:
             self.bins = {s: np.asarray(bins[s]) for s in self.spectra}
         else:
             self.bins = {self.spectra[0]: np.asarray(bins)}
+        from .samplers import check_blackwell_rao
+        check_blackwell_rao(self.blackwell_rao, self.nfields, self.bins)
         self.dls_to_cls_array = np.array([2 * np.pi / (l * (l + 1)) if l != 0 else 0 for l in range(lmax + 1)])
         self.noise_pol = noise_pol
         # TT from a pixel map keeps per-pixel noise (the f4 pixel path); the harmonic
@@ -327,8 +339,10 @@ class GibbsSampler:
         resume, self._resume_state = getattr(self, "_resume_state", None), None
         init = dls_init if isinstance(dls_init, dict) or resume is not None else {self.spectra[0]: dls_init}
         kw = {"n_warmup": self.n_warmup, "target_accept": self.target_accept} if self.n_warmup else {}
-        if self.summary is not None:
+        if self.summary is not None or self.blackwell_rao is not None:
             kw.update(summary=self.summary, keep_history=self.keep_history)
+        if self.blackwell_rao is not None or self.keep_scales:
+            kw.update(blackwell_rao=self.blackwell_rao, keep_scales=self.keep_scales)
         first = runner.iteration if resume is None else int(resume["iteration"])
         h, acc, t = runner.run(init, self.n_iter, timings=True,
                                gather=self.shard.gather if self.shard is not None else None, resume=resume, **kw)
@@ -398,6 +412,14 @@ class GibbsSampler:
         if self.summary is not None and (self.mask is not None or getattr(self, "tt_pixel", False)):
             raise NotImplementedError("summary: masked and TT-pixel runs keep their histories on the host; the "
                                       "streaming summary covers the full-sky harmonic (all_sph) samplers only")
+        if self.blackwell_rao is not None or self.keep_scales:
+            if self._kind == "noncentered":
+                raise NotImplementedError("blackwell_rao / keep_scales: the non-centered sampler's Metropolis step "
+                                          "has no centered conditional; use CenteredGibbs or ASIS")
+            if self.mask is not None or getattr(self, "tt_pixel", False):
+                raise NotImplementedError("blackwell_rao / keep_scales: masked and TT-pixel runs do not go through "
+                                          "the device C_l draw that records the scales; full-sky harmonic "
+                                          "(all_sph) runs only")
 
     @property
     def posterior_summary(self):
@@ -408,6 +430,25 @@ class GibbsSampler:
         if self._runner is None:
             raise RuntimeError("posterior_summary: nothing has run yet")
         return self._runner.summary(self.shard.gather if self.shard is not None else None)
+
+    @property
+    def blackwell_rao_posterior(self):
+        """After a run with blackwell_rao=: per spectrum {grid, logpdf [nbins, G],
+        mass, alpha [nbins], n, bad} -- log P(D_b = grid | d), the Blackwell-Rao
+        average of the centered conditional over the sky samples of all chains
+        (every rank's when distributed); NaN for TE and bins 0 and 1."""
+        if self._runner is None:
+            raise RuntimeError("blackwell_rao_posterior: nothing has run yet")
+        return self._runner.blackwell_rao(self.shard.gather if self.shard is not None else None)
+
+    @property
+    def h_scales(self):
+        """After a run with keep_scales=True: per spectrum the scale history
+        [n_iter, chains, nbins] (the chain axis dropped for one chain) of the
+        centered conditionals -- beta of the inverse-Gamma spectra, Psi_TT, Psi_EE
+        and Psi_TE of the TEB block; row i belongs to iteration i + 1."""
+        hs = None if self._runner is None else self._runner.h_scales
+        return None if hs is None else {s: self._squeeze(v) for s, v in hs.items()}
 
     @property
     def tuned_proposal_variances(self):

@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from . import _capi as C
-from .engine import GibbsPlan, MH_ORDER, SummaryState
+from .engine import BlackwellRaoState, GibbsPlan, MH_ORDER, SummaryState
 
 INIT_ITER = 0xFFFFFFFF
 ADAPT_KAPPA = 0.6       # Robbins-Monro step n^-kappa of the warm-up adaptation
@@ -65,6 +65,66 @@ def check_summary(summary, keep_history=True):
     if start is not None and int(start) < 0:
         raise ValueError("summary: start must be >= 0")
     return max_lag, None if start is None else int(start)
+
+
+def check_blackwell_rao(br, nfields, bins, dls_init=None, maxbins=None):
+    """run(blackwell_rao=...): None / False (off), {"grid": array [nspec, maxbins,
+    G]} or {"points": G, "span": (lo, hi)} (a geometric grid dls_init[bin] * lo
+    ... * hi per bin), either with an optional "start" (as the summary's).
+    Returns None or {grid, alpha, half_mask, start}; grid is None when the
+    points form is given without dls_init (the constructors' early check)."""
+    from .engine import SPECTRA, br_shapes
+    if br is None or br is False:
+        return None
+    if not isinstance(br, dict):
+        raise ValueError("blackwell_rao: a dict {grid} or {points, span} is needed")
+    bad = set(br) - {"grid", "points", "span", "start"}
+    if bad:
+        raise ValueError(f"blackwell_rao: unknown options {sorted(bad)}")
+    if ("grid" in br) == ("points" in br):
+        raise ValueError("blackwell_rao: give either grid or points (with span)")
+    start = br.get("start")
+    if start is not None and int(start) < 0:
+        raise ValueError("blackwell_rao: start must be >= 0")
+    spectra = SPECTRA[int(nfields)]
+    alpha, half = br_shapes(nfields, bins, maxbins)
+    nspec, maxbins = alpha.shape
+    used = ~np.isnan(alpha)
+    if "grid" in br:
+        if "span" in br:
+            raise ValueError("blackwell_rao: span belongs to the points form")
+        grid = np.array(br["grid"], dtype=np.float64)
+        if grid.ndim != 3 or grid.shape[:2] != (nspec, maxbins):
+            raise ValueError(f"blackwell_rao: grid must be [nspec, maxbins, G] = [{nspec}, {maxbins}, G]")
+        G = grid.shape[2]
+        if not 1 <= G <= 64:
+            raise ValueError("blackwell_rao: the grid points G must lie in [1, 64]")
+        g = grid[used]
+        if not (np.all(np.isfinite(g)) and np.all(g > 0)):
+            raise ValueError("blackwell_rao: grid values must be positive and finite")
+        if G > 1 and not np.all(np.diff(g, axis=1) > 0):
+            raise ValueError("blackwell_rao: grid values must increase along the last axis")
+        grid[~used] = 1.0
+    else:
+        G = int(br["points"])
+        if not 1 <= G <= 64:
+            raise ValueError("blackwell_rao: points G must lie in [1, 64]")
+        lo, hi = (float(v) for v in br.get("span", (0.25, 4.0)))
+        if not (0.0 < lo <= hi and np.isfinite(hi)) or (G > 1 and lo == hi):
+            raise ValueError("blackwell_rao: span must be (lo, hi) with 0 < lo < hi")
+        grid = None
+        if dls_init is not None:
+            d0 = dls_init[0] if isinstance(dls_init, (list, tuple)) else dls_init
+            grid = np.ones((nspec, maxbins, G))
+            fac = np.geomspace(lo, hi, G)
+            for k, s in enumerate(spectra):
+                v = np.asarray(d0[s], dtype=np.float64)
+                u = used[k, :len(v)]
+                if not (np.all(np.isfinite(v[u])) and np.all(v[u] > 0)):
+                    raise ValueError(f"blackwell_rao: dls_init[{s}] must be positive on the drawn bins to centre "
+                                     "a grid on it (give grid= instead)")
+                grid[k, :len(v)][u] = v[u, None] * fac
+    return {"grid": grid, "alpha": alpha, "half_mask": half, "start": None if start is None else int(start)}
 
 
 def warmup_of_state(st):
@@ -146,6 +206,12 @@ class BatchedRunner:
         # and the iteration after which it summarises
         self._summary = None
         self.summary_start = 0
+        # streaming Blackwell-Rao posteriors (run(blackwell_rao=...)): the device
+        # state, the iteration after which it accumulates, and the scale history
+        # of run(keep_scales=True)
+        self._br = None
+        self.br_start = 0
+        self.h_scales = None
 
     def __del__(self):
         # dropped inside another sampler's capture: keep the kept hipGraphs, the
@@ -209,6 +275,10 @@ class BatchedRunner:
         if self._summary is not None:
             st.update(summary_state=self._summary.data.cpu().clone(), summary_max_lag=self._summary.max_lag,
                       summary_start=int(self.summary_start))
+        if self._br is not None:
+            br = self._br
+            st.update(br_state=br.data.cpu().clone(), br_grid=br.grid.cpu().clone(), br_alpha=br.alpha.cpu().clone(),
+                      br_half_mask=int(br.half_mask), br_start=int(self.br_start))
         if self.rng == "replay":
             name, keys, pos, has_gauss, cached = np.random.get_state()
             st.update(numpy_rng_keys=torch.from_numpy(np.asarray(keys, dtype=np.int64)), numpy_rng_pos=int(pos),
@@ -254,6 +324,13 @@ class BatchedRunner:
             self.summary_start = int(st["summary_start"])
         else:
             self._summary = None
+        # likewise a state without Blackwell-Rao keys is "off"
+        if st.get("br_state") is not None:
+            self._br = BlackwellRaoState(p.nchains, st["br_grid"], st["br_alpha"], int(st["br_half_mask"]),
+                                         device=p.device, data=st["br_state"])
+            self.br_start = int(st["br_start"])
+        else:
+            self._br = None
         if self.rng == "replay" and "numpy_rng_keys" in st:
             np.random.set_state(("MT19937", st["numpy_rng_keys"].numpy().astype(np.uint32), st["numpy_rng_pos"],
                                  st["numpy_rng_has_gauss"], st["numpy_rng_cached"]))
@@ -364,6 +441,35 @@ class BatchedRunner:
             res[s]["n"] = n
         return res
 
+    # -- streaming Blackwell-Rao posteriors -----------------------------------------------
+    def _br_update(self, scales, capacity, it0, k):
+        """Accumulate iterations it0 + 1 .. it0 + k (in the scale ring) except
+        those up to br_start."""
+        first = max(it0, self.br_start) + 1
+        n = it0 + k - first + 1
+        if n > 0:
+            self._br.update(scales, capacity, first, n)
+
+    def blackwell_rao(self, gather=None):
+        """The Blackwell-Rao marginal posteriors of the last run(blackwell_rao=...):
+        per spectrum a dict of numpy arrays -- grid, logpdf [nbins, G], mass,
+        alpha [nbins] -- with n, the iterations per chain, and bad, the rows
+        this rank's chains skipped for a non-positive or non-finite scale.
+        logpdf is log P(D_b = grid | d); NaN where no one-dimensional
+        conditional exists (TE, bins 0 and 1).  gather as in summary()."""
+        if self._br is None:
+            raise RuntimeError("blackwell_rao: the last run() kept no Blackwell-Rao state (run(blackwell_rao=...))")
+        p, br = self.plan, self._br
+        out = br.finish(gather if gather is not None else self._gather)
+        lp, mass = out["logpdf"].cpu().numpy(), out["mass"].cpu().numpy()
+        grid, alpha, bad = br.grid.cpu().numpy(), br.alpha.cpu().numpy(), br.bad().cpu().numpy()
+        res = {}
+        for i, s in enumerate(p.spectra):
+            nb = len(p.bins[s]) - 1
+            res[s] = {"grid": grid[i, :nb].copy(), "logpdf": lp[i, :nb].copy(), "mass": mass[i, :nb].copy(),
+                      "alpha": alpha[i, :nb].copy(), "n": out["n"], "bad": int(bad[:, i].sum())}
+        return res
+
     def summary_accept_counts(self, gather=None):
         """(counts per spectrum {s: int64 [chains, flags]}, n) of the summarised
         iterations (None for the centered sampler)."""
@@ -472,7 +578,7 @@ class BatchedRunner:
 
     # -- a whole run --------------------------------------------------------------------
     def run(self, dls_init, n_iter, timings=False, gather=None, graph_chunk=32, resume=None, n_warmup=0,
-            target_accept=0.25, summary=None, keep_history=True):
+            target_accept=0.25, summary=None, keep_history=True, blackwell_rao=None, keep_scales=False):
         """n_iter iterations from dls_init; returns (histories, accepts[, step
         times]).  gather: ShardContext.gather of a torchrun job -- the device
         histories of every rank are all-gathered along the chain axis (global
@@ -494,10 +600,26 @@ class BatchedRunner:
         row are not summarised.  A resumed state that carries a summary continues
         it; a run without resume starts a new one.  keep_history=False (needs a
         summary): no history is allocated on the device or the host and the
-        histories and accepts are returned as None."""
+        histories and accepts are returned as None.
+        blackwell_rao: None, {"grid": [nspec, maxbins, G]} or {"points": G, "span":
+        (lo, hi)}, either with "start" (as the summary's) -- the streaming
+        Blackwell-Rao marginal posterior of every drawn bin on a grid of G <= 64
+        values (runner.blackwell_rao()): the C_l draw records the scale of its
+        conditional in a ring beside the trace ring, and the state is updated
+        from it after every chunk replay / eager step.  Centered and ASIS only.
+        It also lifts the need for a summary of keep_history=False.  A resumed
+        state that carries one continues it.  keep_scales: keep the scale history
+        {spectrum: [n_iter, chains, nbins]} in runner.h_scales (row i belongs to
+        the run's iteration i + 1; the start has no scale)."""
         p = self.plan
         n_warmup = check_warmup(self.kind, self.rng, n_warmup, target_accept)
-        sm_opts = check_summary(summary, keep_history)
+        br_opts = check_blackwell_rao(blackwell_rao, p.F, p.bins, dls_init, p.maxbins)
+        if (br_opts is not None or keep_scales) and self.kind == "noncentered":
+            raise NotImplementedError("blackwell_rao / keep_scales: the non-centered sampler has no centered "
+                                      "conditional draw (use the centered or the ASIS sampler)")
+        sm_opts = check_summary(summary, keep_history or br_opts is not None)
+        if p.scale_trace is not None:
+            p.cls_scale_trace(None)         # left attached by a run that raised
         self._gather = gather
         if resume is not None:
             self.load_state_dict(resume)
@@ -518,9 +640,23 @@ class BatchedRunner:
             else:
                 self._summary_alloc(sm_opts[0])
                 self.summary_start = self.n_warmup if sm_opts[1] is None else sm_opts[1]
-        sm = self._summary
-        if sm is None and not keep_history:
+        if resume is None or self._br is None:
+            if br_opts is None:
+                self._br = None
+            else:
+                if br_opts["grid"] is None:
+                    raise ValueError("blackwell_rao: the points form needs dls_init to centre its grid on")
+                self._br = BlackwellRaoState(p.nchains, br_opts["grid"], br_opts["alpha"], br_opts["half_mask"],
+                                             device=p.device)
+                self.br_start = self.n_warmup if br_opts["start"] is None else br_opts["start"]
+        sm, br = self._summary, self._br
+        if br is not None and self.kind == "noncentered":
+            raise NotImplementedError("blackwell_rao: the non-centered sampler has no centered conditional draw")
+        if sm is None and br is None and not keep_history:
             raise ValueError("keep_history=False needs a summary")
+        with_scales = br is not None or keep_scales
+        self.h_scales = None
+        Hs = p.zeros(n_iter, p.nchains, p.nspec, p.maxbins) if keep_scales else None
         # steps of this run that adapt; warm-up and frozen steps never share a graph
         n_adapt = min(max(self.n_warmup - self.iteration, 0), n_iter)
         with_start = self.kind != "asis"
@@ -547,19 +683,28 @@ class BatchedRunner:
                 cache["trace"] = p.zeros(chunk, p.nchains, p.nspec, p.maxbins)
                 cache["acc"] = p.zeros(chunk, p.nchains, max(p.nacc, 1), dtype=torch.int32)
             trace, acc_tr = cache["trace"], cache["acc"]
+            # the scale ring beside the trace ring; graphs captured with it attached
+            # hold its pointer and are cached under keys of their own
+            sc_tr = cache.setdefault("scales", p.zeros(chunk, p.nchains, p.nspec, p.maxbins)) if with_scales else None
             # single-rank runs: each finished chunk of the histories goes to pinned
             # host memory on a copy stream while the next chunk computes (only the
             # last chunk's transfer is left after the loop)
             if gather is None and keep_history:
                 Hh = torch.empty(H.shape, dtype=H.dtype, pin_memory=True)
                 Ah = torch.empty(A.shape, dtype=A.dtype, pin_memory=True)
+            if gather is None and (keep_history or keep_scales):
                 cs = cache.setdefault("copy_stream", torch.cuda.Stream())
+            if gather is None and keep_scales:
+                Sh = torch.empty(Hs.shape, dtype=Hs.dtype, pin_memory=True)
             p.iteration_counter(True, self.iteration + 1)
+            p.cls_scale_trace(sc_tr, chunk)
             done = 0
             while done < n_iter:
                 adapt = done < n_adapt
                 k = min(chunk, (n_adapt if adapt else n_iter) - done)
                 key = ("adapt", k) if adapt else k
+                if with_scales:
+                    key = ("scales", key)
                 if key not in cache:
                     cache[key] = self.capture_steps(k, trace=trace, trace_capacity=chunk, accept_trace=acc_tr,
                                                     adapt=adapt)
@@ -576,6 +721,10 @@ class BatchedRunner:
                     # one launch on the run's stream: the chunk's rows of the ring
                     # and its accept flags (the captured graphs are not touched)
                     self._summary_update(trace, chunk, self.iteration - k, k, acc_tr, acc_tr.stride(0))
+                if br is not None:
+                    self._br_update(sc_tr, chunk, self.iteration - k, k)
+                if keep_scales:
+                    Hs[done:done + k].copy_(sc_tr[:k] if r0 == 0 else sc_tr[(torch.arange(k) + r0) % chunk])
                 h0, h1 = (0 if done == 0 else off + done), off + done + k
                 if keep_history:
                     if r0 == 0:
@@ -590,6 +739,12 @@ class BatchedRunner:
                     with torch.cuda.stream(cs):
                         Hh[h0:h1].copy_(H[h0:h1], non_blocking=True)
                         Ah[done:done + k].copy_(A[done:done + k], non_blocking=True)
+                if gather is None and keep_scales:
+                    ev = torch.cuda.Event()
+                    ev.record()
+                    cs.wait_event(ev)
+                    with torch.cuda.stream(cs):
+                        Sh[done:done + k].copy_(Hs[done:done + k], non_blocking=True)
                 if timings:
                     e1.synchronize()
                     t_steps += [e0.elapsed_time(e1) * 1e-3 / k] * k
@@ -599,15 +754,27 @@ class BatchedRunner:
                 self.accept.copy_(acc_tr[k - 1][:, :self.accept.shape[1]])
             self.graph = None
             p.iteration_counter(False)
+            p.cls_scale_trace(None)
             n_iter = 0
-            if gather is None and keep_history:
+            if gather is None and (keep_history or keep_scales):
                 cs.synchronize()
+            if gather is None and keep_history:
                 H, A = Hh, Ah
+            if gather is None and keep_scales:
+                Hs = Sh
+        # eager steps: a one-row scale ring, as the chain's D_l is a one-row trace
+        sc1 = p.zeros(1, p.nchains, p.nspec, p.maxbins) if with_scales and n_iter > 0 else None
+        if sc1 is not None:
+            p.cls_scale_trace(sc1, 1)
         for i in range(n_iter):
             t0 = time.perf_counter() if timings else 0.0
             self.step()
             if i < n_adapt:
                 p.mh_adapt(self.accept)
+            if br is not None:
+                self._br_update(sc1, 1, self.iteration - 1, 1)
+            if keep_scales:
+                Hs[i].copy_(sc1[0])
             if sm is not None:
                 # the chain's D_l as a one-row trace
                 self._summary_update(self.dl, 1, self.iteration - 1, 1, self.accept, 0)
@@ -618,6 +785,11 @@ class BatchedRunner:
             if timings:
                 torch.cuda.synchronize()
                 t_steps.append(time.perf_counter() - t0)
+        if sc1 is not None:
+            p.cls_scale_trace(None)
+        if keep_scales:
+            Sn = (Hs if gather is None else gather(Hs, dim=1)).cpu().numpy()
+            self.h_scales = {s: Sn[:, :, k, :len(p.bins[s]) - 1] for k, s in enumerate(p.spectra)}
         if not keep_history:
             if timings:
                 torch.cuda.synchronize()

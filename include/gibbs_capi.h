@@ -140,6 +140,24 @@ int gs_sweep_stats(gs_plan* plan, const double* d_alm, const double* s, double* 
 /* centered C_l draw (inverse-Gamma; TEB: inverse-Wishart TT/EE/TE) */
 int gs_cls_draw(gs_plan* plan, const double* stats, const double* invgamma_replay,
                 uint64_t seed, uint32_t iteration, double* dl_binned_out, void* stream);
+/* Scale trace of the centered C_l draw: a caller-owned DEVICE ring scales
+ * [capacity][nchains][nspec][maxbins] (fp64, the layout of the D_l trace ring)
+ * attached to the plan.  While it is attached, every C_l draw of the plan --
+ * gs_cls_draw, gs_step_centered[_fused], gs_step_asis[_fused] -- records, in
+ * the launch that holds the sums and in slot (iteration - 1) % capacity, the
+ * scale of the conditional it samples (CenteredGibbs.py:54-93):
+ *   inverse-Gamma spectra (T alone; EE, BB of EB; BB of TEB): beta_b =
+ *     sum_{l in b} l(l+1)/(4 pi) sum_m s_lm^2, the bits that multiply the
+ *     variate (a replayed draw is dl == scales * invgamma_replay bit for bit);
+ *   the TEB block: the entries of the inverse-Wishart scale Psi_b =
+ *     sum_{l in b} l(l+1)/(2 pi) sum_m s_lm s_lm^T -- Psi_TT in the TT slot,
+ *     Psi_EE in the EE slot, Psi_TE in the TE slot;
+ *   bins 0, 1 and the bins past a spectrum's count: 0.
+ * scales NULL detaches the ring; with none attached the draw stores nothing
+ * more and every output keeps its bits.  A captured graph holds the pointer as
+ * a kernel argument, so attach or detach between captures: the call fails
+ * while `stream` (the stream the steps are launched on) is being captured. */
+int gs_cls_scale_trace(gs_plan* plan, double* scales, int capacity, void* stream);
 /* non-centered Metropolis-within-Gibbs over blocks (in/out dl_binned) */
 /* proposals of the NC Metropolis step (NonCenteredGibbs.py:292-330) into caller
  * buffers [nchains][nspec][maxbins] (prop, log proposal ratio) and, when
@@ -332,6 +350,46 @@ int gs_summary_update(void* state, int nchains, int nspec, int maxbins, int nacc
                       long long accept_stride, void* stream);
 int gs_summary_finish(const void* state, int C, int nspec, int maxbins, int max_lag, double* pooled,
                       double* chain_mean, double* chain_var, double* acf, double* gamma, void* stream);
+
+/* ---- streaming Blackwell-Rao marginal posteriors of the D_l (gs_br.hip) -------
+ * The centered C_l draw samples D_b | s from an inverse-Gamma(alpha_b, beta_b)
+ * (PolarizedCenteredClsSampler.sample, CenteredGibbs.py:54-93); the Blackwell-Rao
+ * estimate averages that density over the sky samples,
+ *   P(D_b | d) ~ 1/N sum_i IG(D_b; alpha_b, beta_b,i),
+ * on a grid of G values per (spectrum, bin), 1 <= G <= 64.  Plan-independent:
+ * any scale ring [capacity][nchains][nspec][maxbins] (gs_cls_scale_trace) is
+ * accumulated.  DEVICE fp64 inputs: grid [nspec][maxbins][G] (D_g > 0,
+ * increasing) and alpha [nspec][maxbins], the shape of each bin's conditional
+ * -- n_b / 2 - 1 with n_b = l1^2 - l0^2 for the inverse-Gamma spectra, n_b / 2
+ * - 2 for TT and EE of the TEB block (the diagonal of an inverse-Wishart(Psi,
+ * nu = n_b - 3) in two dimensions is inverse-Gamma((nu - 1) / 2, Psi_ii / 2)),
+ * NaN for TE, bins 0, 1 and unused bins, which are skipped and finish as NaN.
+ * half_mask: bit k set halves the recorded scale of spectrum k (TEB: TT and EE).
+ * The state is a caller-owned DEVICE buffer of gs_br_bytes bytes: 8 header
+ * doubles (int64 iteration count first), then per (chain, spectrum, bin, g),
+ * g fastest, the running maximum m and S = sum_i exp(t_i - m) of
+ * t_i = alpha log beta_i - beta_i / D_g (two planes: all m, then all S;
+ * 16 B x nchains x nspec x maxbins x G), then int64 bad [nchains][nspec], the
+ * rows skipped because beta <= 0 or not finite.  gs_br_reset zeroes it.
+ * gs_br_update adds iterations first_iteration ... first_iteration + nsteps - 1
+ * (iteration it in slot (it - 1) % capacity; nsteps <= capacity) in one launch,
+ * per state element in iteration order: the state's bits do not depend on how
+ * the iterations were cut into launches.  Successive updates of one state must
+ * be ordered on one stream.
+ * gs_br_finish, over the C chains of a state (a state whose planes were
+ * all-gathered along the chain axis is finished over every rank's chains):
+ *   logpdf [nspec][maxbins][G] = logsumexp_c,i t - log(C n) - lgamma(alpha)
+ *                                - (alpha + 1) log D_g
+ *   mass   [nspec][maxbins]    the trapezoid integral of exp(logpdf) over the
+ *                              bin's grid (near 1 when the grid covers the posterior)
+ * gs_br.hip documents the layout and the order of every operation. */
+int gs_br_bytes(int nchains, int nspec, int maxbins, int G, long long* bytes /* HOST */);
+int gs_br_reset(void* state, int nchains, int nspec, int maxbins, int G, void* stream);
+int gs_br_update(void* state, int nchains, int nspec, int maxbins, int G, const double* grid, const double* alpha,
+                 unsigned half_mask, const double* scales, int capacity, uint32_t first_iteration, int nsteps,
+                 void* stream);
+int gs_br_finish(const void* state, int C, int nspec, int maxbins, int G, const double* grid, const double* alpha,
+                 double* logpdf, double* mass, void* stream);
 
 /* device-side timing of the dominant kernel: with enable = 1 every later CR-sweep
  * launch is bracketed by hipEvents on its stream (also while the stream is
