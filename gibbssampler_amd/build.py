@@ -22,7 +22,7 @@ SOURCES = [os.path.join(HERE, "csrc", "gs_kernels.hip"), os.path.join(HERE, "csr
            os.path.join(HERE, "csrc", "gs_masked.hip"), os.path.join(HERE, "csrc", "gs_summary.hip"),
            os.path.join(HERE, "csrc", "gs_br.hip")]
 HEADERS = [os.path.join(HERE, "csrc", h) for h in ("gs_rng.h", "gs_common.h", "gs_bm_tables.h", "gs_block.h",
-                                                         "gs_launch.h")] + \
+                                                         "gs_launch.h", "gs_sweep_pack.h")] + \
     [os.path.join(ROOT, "include", "gibbs_capi.h")]
 LIB = os.path.join(HERE, "libgibbs_hip.so")
 ARCH = os.environ.get("GIBBS_OFFLOAD_ARCH", "gfx950")

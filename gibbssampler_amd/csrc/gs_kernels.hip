@@ -29,6 +29,7 @@
 #include "gs_common.h"
 #include "gs_block.h"
 #include "gs_launch.h"
+#include "gs_sweep_pack.h"
 
 using namespace gs;
 
@@ -113,6 +114,15 @@ struct gs_plan {
     int npair = 0, ntile = 0, nchunk = 0, rows_per_task = 64;
     int sweep_tw = 4, nchunkg = 0;   // tiles per sweep workgroup, chunks per tile
     int ntask = 0;                   // valid (tile, chunk) waves per chain
+    // the grid of the native no-map throughput sweep with its diagonal workgroups
+    // packed (gs_sweep_pack.h; null: option GS_SWEEP_PACK=0, or tw != 1): packed
+    // pair k is the task (-2 - k, 0); pack_tab holds the packed pairs' int4
+    // (tile, chunk group, offset of its thread words in pack_tab, absorbs the
+    // next chunk group's single entry), then the thread words by class
+    int2* tasks_pk = nullptr;
+    int npair_pk = 0;
+    int npacked = 0, nabsorb = 0;    // packed workgroups / absorbed one-entry groups per chain
+    int* pack_tab = nullptr;
     // workspace
     double* partials = nullptr;      // [nchains][ntile][nchunkg][nstat or raw sums][64]
     // raw-moment statistics of native-draw NC steps (GS_NC_RAW=0|1, default 1):
@@ -472,7 +482,12 @@ struct SweepOp {
 // every row of the workgroup is one contiguous 4 KiB run per field and chain;
 // consecutive workgroups are consecutive chains of the same task and share the
 // data reads in L2.  Each wave writes its 64 l's statistic partials of its
-// chunk; k_stats_finish sums them in a fixed order.
+// chunk; k_stats_finish sums them in a fixed order.  With tw = 1 (the default:
+// 1 tile x 4 chunks, wave = chunk) the workgroups that touch the diagonal l = m
+// would issue every row of every chunk-wave for the lanes l >= m that remain;
+// the native no-map throughput sweep runs them in the packed form instead
+// (cr_sweep_packed below; gs_sweep_pack.h builds its table), selected per task
+// pair, so the off-diagonal workgroups keep their loop as it is.
 // the operator of this lane's l: from the chain's D_l (op.mode >= 0) or the table
 template <int F>
 __device__ __forceinline__ void sweep_operator(bool ok, int chain, int ell, int L, const double* __restrict__ params,
@@ -691,10 +706,94 @@ constexpr int SW_TL_MAX = 16384;
 __device__ unsigned long long g_sw_tl[4 * SW_TL_MAX];
 #endif
 
+// Packed form of a diagonal workgroup (tw = 1; native draws, no map): the 256
+// column segments (l, chunk) of the (tile, chunk group) are dealt over the 256
+// threads longest first (gs_sweep_pack.h), so a wave's row loop is as long as
+// its own longest segment instead of every chunk-wave issuing all its rows for
+// a shrinking set of lanes.  A lane's draw depends on its own (l, m) alone (the
+// Philox counter, the data offset, the accumulators), so the lane that runs a
+// segment forms the same sums in the same order (rows ascending from 0.0) as
+// the lane of the chunk-wave that owned it.  Every thread owns one (chunk, l)
+// slot of `red` (an empty segment: zeros), and 64 threads add the four chunk
+// planes as sweep_partials_store does, ((c0 + c1) + c2) + c3, into the same
+// partial slot.  pd.w: this workgroup also takes the single entry (l_hi, l_hi)
+// of the next chunk group (the tile's last) and writes that partial slot too.
+template <int F, bool RAW, int NPLANE>
+__device__ __forceinline__ void cr_sweep_packed(int chain, int4 pd, const int* __restrict__ pack, int L, int ntile,
+                                                int nchunkg, int tm, const double* __restrict__ d,
+                                                const double* __restrict__ params, double* __restrict__ partials,
+                                                uint32_t seed_lo, uint32_t seed_hi, uint32_t iter, uint32_t substep,
+                                                int chain0, const SweepOp& op, const double* __restrict__ tab,
+                                                double* red) {
+    static_assert(NPLANE == 4, "the packed form sums four chunk planes of `red`");
+    constexpr int NS = SweepAcc<F>::n(RAW);
+    const int t = pd.x, cg = pd.y;
+    const gs_pack::Word wd = gs_pack::decode((uint32_t)pack[pd.z + (int)threadIdx.x]);
+    const int trips = __builtin_amdgcn_readfirstlane(wd.trips);     // one value per wave
+    const int lhi = L - WAVE * t;
+    const int ell = wd.single ? lhi : lhi - 63 + wd.lt;
+    int m = (wd.single ? 4 * cg + 4 : 4 * cg + wd.cq) * tm;
+    int cnt = wd.cnt;
+    GS_ASSERT(t < ntile && cg + (pd.w ? 1 : 0) < nchunkg && (cnt == 0 || (ell >= 0 && m + cnt - 1 <= ell)));
+    const long long NR = (long long)(L + 1) * (L + 1);
+    const Key key = chain_key(seed_lo, seed_hi, (uint32_t)(chain0 + chain));
+    const uint32_t tag = TAG_CR | (substep << 8);
+    double pm[NP];
+    sweep_operator<F>(!RAW && cnt > 0, chain, max(ell, 0), L, params, op, pm);
+    double acc[NS];
+#pragma unroll
+    for (int q = 0; q < NS; ++q) acc[q] = 0.0;
+    double dv[F][2];
+    if (cnt > 0 && m == 0) {
+        load_d<F, 1>(d, NR, ell, dv);
+        sweep_entry<F, 0, false, 1, RAW>(dv, nullptr, nullptr, NR, ell, (uint32_t)ell, tag, iter, key, pm, acc, tab);
+        m = 1;
+        --cnt;
+    }
+    const char* db[F];
+#pragma unroll
+    for (int f = 0; f < F; ++f) db[f] = reinterpret_cast<const char*>(d + (size_t)f * (size_t)NR);
+    GS_ASSERT(NR * 8 < (1ll << 32));
+    uint32_t i32 = (uint32_t)((long long)m * (2 * L + 1 - m) / 2 + ell);
+    for (int j = 0; j < trips; ++j) {
+        if (j < cnt) {
+            const uint32_t r = 2u * i32 - (uint32_t)(L + 1);
+            GS_ASSERT((long long)r + 1 < NR && (long long)r > L);
+            load_d2_off<F>(db, r * 8u, dv);
+            sweep_entry<F, 0, false, 2, RAW>(dv, nullptr, nullptr, NR, (long long)r, i32, tag, iter, key, pm, acc, tab);
+        }
+        i32 += (uint32_t)(L - m);
+        ++m;
+    }
+    double* po = partials + (((long long)chain * ntile + t) * nchunkg + cg) * NS * WAVE;
+#pragma unroll
+    for (int q = 0; q < NS; ++q) red[(wd.cq * NS + q) * WAVE + wd.lt] = wd.single ? 0.0 : acc[q];
+    if (wd.single)
+#pragma unroll
+        for (int q = 0; q < NS; ++q) po[(NS + q) * WAVE + 63] = acc[q];
+    __syncthreads();
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (w == 0) {
+#pragma unroll
+        for (int q = 0; q < NS; ++q) {
+            double v = red[q * WAVE + lane];
+            for (int k = 1; k < 4; ++k) v += red[(k * NS + q) * WAVE + lane];
+            po[q * WAVE + lane] = v;
+        }
+    } else if (w == 1 && pd.w && lane < 63) {
+        // the absorbed chunk group's other 63 l: what its idle lanes summed
+#pragma unroll
+        for (int q = 0; q < NS; ++q) po[(NS + q) * WAVE + lane] = 0.0;
+    }
+}
+
 // one (tile group, row chunk) task of one chain: logical workgroup wg
-template <int F, int ZM, bool STORE, bool RAW = false>
+// (a packed pair, gc.x < -1, only in the task list of the native no-map form;
+// NPLANE: the chunk planes `red` holds, sweep_red_planes)
+template <int F, int ZM, bool STORE, bool RAW = false, int NPLANE = 3>
 __device__ __forceinline__ void cr_sweep_task(int wg, int L, int nchains, int ntile, int nchunkg, int tm, int tw,
-                                              const int2* __restrict__ tasks, const double* __restrict__ d,
+                                              const int2* __restrict__ tasks, const int* __restrict__ pack,
+                                              const double* __restrict__ d,
                                               const double* __restrict__ params, const double* __restrict__ z,
                                               double* __restrict__ s, double* __restrict__ partials,
                                               uint32_t seed_lo, uint32_t seed_hi, uint32_t iter, uint32_t substep,
@@ -705,7 +804,14 @@ __device__ __forceinline__ void cr_sweep_task(int wg, int L, int nchains, int nt
     const int chain = wg % nchains;
     const int lane = threadIdx.x & 63;
     const int2 gc = tasks[pair];
-    if (gc.x < 0) return;                       // padding pair (whole workgroup)
+    if (gc.x < 0) {                             // padding pair (whole workgroup), or a packed one
+        if constexpr (ZM == 0 && !STORE && NPLANE == 4) {
+            if (gc.x < -1)
+                cr_sweep_packed<F, RAW, NPLANE>(chain, reinterpret_cast<const int4*>(pack)[-2 - gc.x], pack, L, ntile, nchunkg,
+                                        tm, d, params, partials, seed_lo, seed_hi, iter, substep, chain0, op, tab, red);
+        }
+        return;
+    }
     const int w = threadIdx.x >> 6, cw = 4 / tw;
     const int t = tw * gc.x + w % tw;
     const bool tile_ok = t < ntile;
@@ -807,7 +913,8 @@ __device__ __forceinline__ void cr_sweep_task(int wg, int L, int nchains, int nt
 #endif
 template <int F, int ZM, bool STORE, int PRE = 0, bool RAW = false>
 __global__ __launch_bounds__(256, GS_SWEEP_MINW) void k_cr_sweep(int L, int nchains, int ntile, int nchunkg, int tm, int tw,
-                                                  const int2* __restrict__ tasks, const double* __restrict__ d,
+                                                  const int2* __restrict__ tasks, const int* __restrict__ pack,
+                                                  const double* __restrict__ d,
                                                   const double* __restrict__ params, const double* __restrict__ z,
                                                   double* __restrict__ s, double* __restrict__ partials,
                                                   uint32_t seed_lo, uint32_t seed_hi, IterArg itarg, uint32_t substep,
@@ -821,7 +928,9 @@ __global__ __launch_bounds__(256, GS_SWEEP_MINW) void k_cr_sweep(int L, int ncha
     const uint32_t iter = itarg.get();
     constexpr int NS = SweepAcc<F>::n(RAW);
     __shared__ __attribute__((aligned(16))) double tab[ZM == 0 ? BM_TAB_DOUBLES : 2];
-    __shared__ double red[3 * NS * WAVE];           // chunk-wave sums of tw < 4 shapes
+    // chunk-wave sums of tw < 4 shapes (3 planes); the packed form's 4 chunk planes
+    constexpr int NPLANE = ZM == 0 && !STORE && PRE == 0 ? 4 : 3;
+    __shared__ double red[NPLANE * NS * WAVE];
     if constexpr (PRE > 0) {
         static_assert(ZM == 0, "latency form: native draws only");
         // the variate workgroups sit at the END of the grid, so the sweep's
@@ -851,8 +960,9 @@ __global__ __launch_bounds__(256, GS_SWEEP_MINW) void k_cr_sweep(int L, int ncha
 #if defined(GS_SWEEP_WGTIME)
     const unsigned long long tl0 = wall_clock64();
 #endif
-    cr_sweep_task<F, ZM, STORE, RAW>(base + (bid >> 3), L, nchains, ntile, nchunkg, tm, tw, tasks, d, params, z, s,
-                                partials, seed_lo, seed_hi, iter, substep, chain0, op, tab, red);
+    cr_sweep_task<F, ZM, STORE, RAW, NPLANE>(base + (bid >> 3), L, nchains, ntile, nchunkg, tm, tw, tasks, pack, d,
+                                             params, z, s, partials, seed_lo, seed_hi, iter, substep, chain0, op, tab,
+                                             red);
 #if defined(GS_SWEEP_WGTIME)
     __syncthreads();
     if (threadIdx.x == 0 && bid < SW_TL_MAX) {
@@ -2420,7 +2530,7 @@ __global__ void k_record_trace(long long n, const double* __restrict__ dl, doubl
 // ============================================================================
 // the library options (gs_option_set): a fixed set of names
 static const char* const k_options[] = {
-    "GS_SWEEP_TW", "GS_SWEEP_THROUGHPUT", "GS_NC_RAW", "GS_NC_PIPE", "GS_MH_SPLIT", "GS_CLS_PRE", "GS_CLS_PRE_MANY", "GS_F2_GROUP_BYTES",
+    "GS_SWEEP_TW", "GS_SWEEP_PACK", "GS_SWEEP_THROUGHPUT", "GS_NC_RAW", "GS_NC_PIPE", "GS_MH_SPLIT", "GS_CLS_PRE", "GS_CLS_PRE_MANY", "GS_F2_GROUP_BYTES",
     "GS_F2_BATCH_BYTES", "GS_SHT_LDS_FFT_MAX", "GS_SHT_SEG", "GS_SHT_SYN", "GS_SHT_ANA", "GS_SHT_MERGE_RINGS",
     "GS_SHT_CONST_RINGS", "GS_SHT_BLOCKS_MFMA", "GS_SHT_BLK_STAGE", "GS_SHT_FUSED_AUX", "GS_SHT_MFMA_MAX_GB",
     "GS_SHT_RING_TW2"};
@@ -2473,7 +2583,7 @@ void build_tasks(gs_plan* p) {
     // r02 with the workgroup-per-tile statistics finish: NC TEB 32 chains at
     // L 1024: 12 / 16 / 20 / 24 rows 308.5 / 308.5 / 312.0 / 319.3 us per step;
     // centered 1 chain at L 512: 2 / 4 / 8 rows 25.7 / 22.4 / 26.0 us
-    const int tm = L > 512 ? 16 : (L > 256 ? 4 : 8);
+    const int tm = gs_pack::rows_per_chunk(L);      // L > 512 ? 16 : (L > 256 ? 4 : 8)
     p->rows_per_task = tm;
     p->nchunk = L / tm + 1;
     p->ntask = (int)waves(tm);
@@ -2514,24 +2624,57 @@ void build_tasks(gs_plan* p) {
     // the sweep gives XCD x a contiguous range of pairs (all chains of a pair on
     // one XCD); deal the pairs heaviest-first over 8 buckets so every XCD gets
     // the same work, padding with empty pairs (g = -1) to a multiple of 8
-    std::stable_sort(work.begin(), work.end(), [](const auto& a, const auto& b) { return a.first > b.first; });
-    const int per = (int)((work.size() + 7) / 8);
-    std::vector<std::vector<int2>> bucket(8);
-    std::vector<long long> load(8, 0);
-    for (const auto& w : work) {
-        int best = -1;
-        for (int x = 0; x < 8; ++x)
-            if ((int)bucket[x].size() < per && (best < 0 || load[x] < load[best])) best = x;
-        bucket[best].push_back(w.second);
-        load[best] += w.first;
-    }
-    std::vector<int2> tasks;
-    for (int x = 0; x < 8; ++x) {
-        for (const int2& t : bucket[x]) tasks.push_back(t);
-        for (int k = (int)bucket[x].size(); k < per; ++k) tasks.push_back(make_int2(-1, 0));
-    }
+    auto deal = [](std::vector<std::pair<long long, int2>>& work) {
+        std::stable_sort(work.begin(), work.end(), [](const auto& a, const auto& b) { return a.first > b.first; });
+        const int per = (int)((work.size() + 7) / 8);
+        std::vector<std::vector<int2>> bucket(8);
+        std::vector<long long> load(8, 0);
+        for (const auto& w : work) {
+            int best = -1;
+            for (int x = 0; x < 8; ++x)
+                if ((int)bucket[x].size() < per && (best < 0 || load[x] < load[best])) best = x;
+            bucket[best].push_back(w.second);
+            load[best] += w.first;
+        }
+        std::vector<int2> tasks;
+        for (int x = 0; x < 8; ++x) {
+            for (const int2& t : bucket[x]) tasks.push_back(t);
+            for (int k = (int)bucket[x].size(); k < per; ++k) tasks.push_back(make_int2(-1, 0));
+        }
+        return tasks;
+    };
+    const std::vector<int2> tasks = deal(work);
     p->npair = (int)tasks.size();
     dev_upload(&p->tasks, tasks);
+    // the same grid with its diagonal workgroups packed (gs_sweep_pack.h), for the
+    // native no-map throughput sweep at tw = 1 (sweep_launch); every other form
+    // keeps `tasks`.  Option GS_SWEEP_PACK = 0 | 1 (default 1).  A packed
+    // workgroup's work is the wave-rows it issues, in lane-rows like the rest.
+    const char* pk = gs_detail::option("GS_SWEEP_PACK");
+    if (tw != 1 || (pk && atoi(pk) == 0)) return;
+    const gs_pack::Plan P = gs_pack::build(L, tm, true);
+    std::map<std::pair<int, int>, long long> plain_wl;
+    for (const auto& w : work) plain_wl[{w.second.x, w.second.y}] = w.first;
+    std::vector<std::pair<long long, int2>> work_pk;
+    std::vector<int> tab;
+    for (const gs_pack::Group& g : P.groups)
+        if (g.packed) {
+            work_pk.push_back({(long long)WAVE * g.rows_issued, make_int2(-2 - (int)tab.size() / 4, 0)});
+            const int desc[4] = {g.tile, g.cg, g.cls, g.absorb ? 1 : 0};
+            ++p->npacked;
+            p->nabsorb += g.absorb ? 1 : 0;
+            tab.insert(tab.end(), desc, desc + 4);
+        } else {
+            work_pk.push_back({plain_wl.at({g.tile, g.cg}), make_int2(g.tile, g.cg)});
+        }
+    if (tab.empty()) return;                        // (no diagonal workgroup gains: keep one list)
+    const int nd = (int)tab.size();
+    for (int k = 0; k < nd; k += 4) tab[k + 2] = nd + tab[k + 2] * gs_pack::NTHREAD;   // class -> word offset
+    tab.insert(tab.end(), P.table.begin(), P.table.end());
+    const std::vector<int2> tasks_pk = deal(work_pk);
+    p->npair_pk = (int)tasks_pk.size();
+    dev_upload(&p->tasks_pk, tasks_pk);
+    dev_upload(&p->pack_tab, tab);
 }
 
 int check_plan(const gs_plan* p) {
@@ -2546,7 +2689,7 @@ void with_G(const gs_plan* p, Fn&& fn) {
     else fn(std::integral_constant<int, 4>{});
 }
 
-using SweepKernel = void (*)(int, int, int, int, int, int, const int2*, const double*, const double*, const double*,
+using SweepKernel = void (*)(int, int, int, int, int, int, const int2*, const int*, const double*, const double*, const double*,
                              double*, double*, uint32_t, uint32_t, IterArg, uint32_t, int, SweepOp, ClsPre, ProPre, int);
 
 // every k_cr_sweep<F, ZM, STORE, PRE, RAW> the library launches: the latency
@@ -2779,7 +2922,7 @@ int gs_plan_create(const gs_model_desc* desc, gs_plan** out) {
 
 int gs_plan_destroy(gs_plan* p) {
     if (!p) return 0;
-    void* bufs[] = {p->iter_dev, p->ell2blk, p->gbuf, p->phase_tab, p->phase_rng, p->meta, p->bl, p->ell2bin, p->bins, p->blocks, p->prop_sd, p->tasks, p->partials, p->u_nat,
+    void* bufs[] = {p->iter_dev, p->ell2blk, p->gbuf, p->phase_tab, p->phase_rng, p->meta, p->bl, p->ell2bin, p->bins, p->blocks, p->prop_sd, p->tasks, p->tasks_pk, p->pack_tab, p->partials, p->u_nat,
                     p->params, p->stats, p->prop, p->logr, p->dl_tmp, p->cls_var, p->phase_tab_s, p->phase_rng_s, p->dmom,
                     p->bin2blk, p->mh_lam, p->mh_cnt, p->sd_chain};
     for (void* b : bufs)
@@ -2807,6 +2950,13 @@ int gs_plan_sweep_info(const gs_plan* p, int* ntask, int* rows_per_task) {
     if (check_plan(p)) return -1;
     if (ntask) *ntask = p->ntask;
     if (rows_per_task) *rows_per_task = p->rows_per_task;
+    return 0;
+}
+
+int gs_plan_sweep_pack_info(const gs_plan* p, int* npacked, int* nabsorbed) {
+    if (check_plan(p)) return -1;
+    if (npacked) *npacked = p->tasks_pk ? p->npacked : 0;
+    if (nabsorbed) *nabsorbed = p->tasks_pk ? p->nabsorb : 0;
     return 0;
 }
 
@@ -3055,14 +3205,19 @@ static int sweep_launch(gs_plan* p, const SweepReq& r, void* stream) {
         p->defer.raw_dl = r.raw ? r.dl : nullptr;
     }
     const SweepOp op{r.op_mode, p->maxbins, r.dl, p->ell2bin, p->bl, p->kappa[0], p->kappa[1], p->kappa[2]};
-    const int nlog = (int)((long long)p->nchains * p->npair);
-    dim3 g((unsigned)nlog), b(256);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (timing_begin(p, S(stream), &e0, &e1)) return -1;
     const bool rep = r.z != nullptr, st = r.s_out != nullptr;
     // latency form (all loads first) for few chains with short tasks; the
     // throughput form otherwise (more chains: its registers buy occupancy)
     const bool lat = r.op_mode >= 0 && p->rows_per_task <= 4 && !r.given && !rep && p->sweep_latency;
+    // the packed diagonal workgroups: the native-draw throughput form without the
+    // map at tw = 1 (raw moments or not).  GS_SWEEP_TW = 2 | 4, the stored map,
+    // replayed normals, a given map and the latency form keep the plain grid.
+    const bool packed = p->tasks_pk && !lat && !r.given && !rep && !st;
+    const int2* const tasks = packed ? p->tasks_pk : p->tasks;
+    const int nlog = (int)((long long)p->nchains * (packed ? p->npair_pk : p->npair));
+    dim3 g((unsigned)nlog), b(256);
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (timing_begin(p, S(stream), &e0, &e1)) return -1;
     ClsPre cp{};
     ProPre pp{};
     if (r.cls_pre_done) *r.cls_pre_done = false;
@@ -3091,7 +3246,7 @@ static int sweep_launch(gs_plan* p, const SweepReq& r, void* stream) {
     const SweepKernel k =
         with_F(p->F, [&](auto f) { return sweep_variant<decltype(f)::value>(lat, r.given, rep, r.raw, st); });
     hipLaunchKernelGGL(k, g, b, 0, S(stream), p->L, p->nchains, p->ntile, p->nchunkg, p->rows_per_task, p->sweep_tw,
-                       p->tasks, r.d_alm, r.params, r.z, r.s_out, partials, r.seed.lo, r.seed.hi,
+                       tasks, p->pack_tab, r.d_alm, r.params, r.z, r.s_out, partials, r.seed.lo, r.seed.hi,
                        p->ita(r.iteration), r.substep, p->chain0, op, cp, pp, nlog);
     GS_LAUNCH_CHECK("k_cr_sweep");
     if (p->timing && record_ev(e1, S(stream))) return -1;

@@ -90,6 +90,9 @@ class GibbsPlan:
         nt, rpt = ctypes.c_int(), ctypes.c_int()
         C.check(self.lib.gs_plan_sweep_info(h, ctypes.byref(nt), ctypes.byref(rpt)))
         self.ntask, self.rows_per_task = nt.value, rpt.value
+        # packed diagonal workgroups of the no-map throughput sweep, absorbed one-entry groups (per chain)
+        C.check(self.lib.gs_plan_sweep_pack_info(h, ctypes.byref(nt), ctypes.byref(rpt)))
+        self.sweep_packed, self.sweep_absorbed = nt.value, rpt.value
         # host-side replay helpers (data independent)
         ell = np.arange(self.L + 1, dtype=np.float64)
         expo = (2 * ell + 1) / 2

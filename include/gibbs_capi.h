@@ -98,6 +98,8 @@ const char* gs_last_error(void);
  * bit-identity tests compare, plus the f2 / table workspace budgets:
  *   GS_SWEEP_TW          1 | 2 | 4  CR-sweep workgroup shape (tiles x chunks;
  *                                   2 suits --skymap store, 1 the default)
+ *   GS_SWEEP_PACK        0 | 1      packed diagonal workgroups of the native no-map
+ *                                   throughput sweep at GS_SWEEP_TW=1 (default 1)
  *   GS_SWEEP_THROUGHPUT  1          few-chain plans use the throughput form
  *   GS_NC_RAW            0 | 1      raw-moment statistics of native NC sweeps
  *   GS_NC_PIPE           0 | 1      pipelined multi-step NC graphs (gs_nc_steps)
@@ -118,6 +120,10 @@ int gs_plan_destroy(gs_plan* plan);
 int gs_plan_info(const gs_plan* plan, int* maxbins, int* nstat, int* nblocks_total, int* nspec);
 /* tiling of the CR sweep: tasks per chain, m-rows per task */
 int gs_plan_sweep_info(const gs_plan* plan, int* ntask, int* rows_per_task);
+/* the packed grid of the native no-map throughput sweep (option GS_SWEEP_PACK):
+ * per chain, the workgroups that run the packed form and the one-entry chunk
+ * groups they absorb; both 0 where the plan keeps the plain grid alone */
+int gs_plan_sweep_pack_info(const gs_plan* plan, int* npacked, int* nabsorbed);
 
 /* ---- stand-alone layout / expansion helpers (no plan needed) ---------------- */
 int gs_var_expand(int lmax, int n, const double* dl, double* var, void* stream);

@@ -66,9 +66,20 @@ def loop_hist(asm):
     return best
 
 
-def wave_rows(L=1024, nchains=32, tile=64):
-    """every (tile, row m <= l_hi) of the triangle, once per chain"""
-    return nchains * sum(L - tile * t + 1 for t in range((L + tile) // tile) if L - tile * t >= 0)
+def wave_rows(L=1024, nchains=32):
+    """(plain, packed): the wave-rows a launch issues with the plain grid (option
+    GS_SWEEP_PACK=0: every (tile, row m <= l_hi) of the triangle, once per chain)
+    and with the default grid, where the packed diagonal workgroups
+    (csrc/gs_sweep_pack.h) issue each wave's own loop trips (plus its one-slot
+    row m = 0 where it has one) -- a packed wave-row is priced like any other,
+    although some of its lanes may idle.  Counted by the table builder itself
+    (tools/sweep_pack_rows.cpp)."""
+    with tempfile.TemporaryDirectory() as td:
+        exe = os.path.join(td, "sweep_pack_rows")
+        subprocess.run(["g++", "-std=c++17", "-O1", "-I", os.path.join(ROOT, "gibbssampler_amd", "csrc"), "-o", exe,
+                        os.path.join(HERE, "sweep_pack_rows.cpp")], check=True)
+        plain, packed = subprocess.run([exe, str(L)], check=True, capture_output=True, text=True).stdout.split()
+    return nchains * int(plain), nchains * int(packed)
 
 
 def main():
@@ -104,7 +115,7 @@ def main():
         priced[cls][0] += n
         priced[cls][1] += n * rates[cls]
         cyc += n * rates[cls]
-    wr = wave_rows()
+    wr_plain, wr = wave_rows()
     out = {"kernel": "k_cr_sweep<3,0,false,0> row loop (gfx950 ISA of the product source)",
            "valu_instructions_per_row": valu, "non_valu_per_row": other,
            "classes": {k: {"count": v[0], "cycles": round(v[1], 1), "cycles_per_instr": rates[k], "measured_w8": raw[k]}
@@ -113,6 +124,10 @@ def main():
            "microbench_loop_overhead_per_instr": round(ovh, 3),
            "flat4_cycles_per_row": 4 * valu,
            "wave_rows_per_launch": wr,
+           "wave_rows_per_launch_plain": wr_plain,
+           "wave_rows_note": "wave_rows_per_launch (and the two figures below) is the default grid's, with the "
+                             "diagonal workgroups packed; a GS_SWEEP_PACK=0 or GS_SWEEP_TW=2|4 run issues "
+                             "wave_rows_per_launch_plain, so a ceiling priced from this file is 4.4 % low for it",
            "issue_cycles_per_simd": round(cyc * wr / 1024, 0),
            "floor_us_at_2p4GHz": round(cyc * wr / 1024 / 2.4e3, 2),
            "source": "tools/sweep_issue_model.py: ISA class counts x profiles/r06_valu_rate.json (W = 8 rates less "
