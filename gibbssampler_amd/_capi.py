@@ -134,6 +134,11 @@ _SIGS = [
     ("gs_br_update", ctypes.c_int, [_VP] + [ctypes.c_int] * 4 + [_VP, _VP, ctypes.c_uint32, _VP, ctypes.c_int,
                                                                  ctypes.c_uint32, ctypes.c_int, _VP]),
     ("gs_br_finish", ctypes.c_int, [_VP] + [ctypes.c_int] * 4 + [_VP] * 5),
+    ("gs_brl_bytes", ctypes.c_int, [ctypes.c_int] * 2 + [ctypes.POINTER(ctypes.c_longlong)]),
+    ("gs_brl_reset", ctypes.c_int, [_VP] + [ctypes.c_int] * 2 + [_VP]),
+    ("gs_brl_update", ctypes.c_int, [_VP] + [ctypes.c_int] * 5 + [_VP] * 5 + [ctypes.c_int, ctypes.c_uint32,
+                                                                            ctypes.c_int, _VP]),
+    ("gs_brl_finish", ctypes.c_int, [_VP] + [ctypes.c_int] * 2 + [_VP] * 5),
     ("gs_sht_create", ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(_VP)]),
     ("gs_sht_destroy", ctypes.c_int, [_VP]),
     ("gs_sht_info", ctypes.c_int, [_VP, c_int_p, c_int_p, ctypes.POINTER(ctypes.c_longlong),

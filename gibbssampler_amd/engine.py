@@ -569,6 +569,177 @@ class BlackwellRaoState:
         return {"logpdf": logpdf, "mass": mass, "n": self.n}
 
 
+def br_likelihood_mask(nfields, bins, maxbins=None, lrange=None):
+    """The bins a Blackwell-Rao likelihood can use, bool [nspec, maxbins]: every
+    drawn bin (b >= 2, below the spectrum's count), with lrange = (lmin, lmax)
+    only those wholly inside it (l0 >= lmin and l1 - 1 <= lmax)."""
+    spectra = SPECTRA[int(nfields)]
+    nb = [len(bins[s]) - 1 for s in spectra]
+    maxbins = max(nb) if maxbins is None else int(maxbins)
+    mask = np.zeros((len(spectra), maxbins), dtype=bool)
+    for k, s in enumerate(spectra):
+        b = np.asarray(bins[s], dtype=np.int64)
+        ok = np.ones(nb[k], dtype=bool)
+        if lrange is not None:
+            ok = (b[:-1] >= lrange[0]) & (b[1:] - 1 <= lrange[1])
+        mask[k, :nb[k]] = ok
+        mask[k, :2] = False
+    return mask
+
+
+def br_likelihood_tables(nfields, bins, theory, mask):
+    """The tables of the streaming Blackwell-Rao likelihood (gs_brl.hip), numpy
+    fp64 on the host: theory [K, nspec, maxbins] (D^th per model; read on the
+    used bins only), mask bool [nspec, maxbins] (the used bins; bins 0, 1 and
+    those past a spectrum's count never count; the TEB block TT, EE, TE is
+    used as a whole, by TT's row).  Returns {cols [Ju] int32 ascending, kind
+    [Ju] int32, coef [Ju], Y [K, Ju], cst [K]}: with x the scale ring's row,
+    log P(D^th_k | s) = sum_j coef_j log(arg_j) - sum_j x_j Y_kj + cst_k.
+    With n_b = l1^2 - l0^2:
+      inverse-Gamma bin (kind 1): coef = alpha = n_b / 2 - 1, Y = 1 / D,
+        cst += -lgamma(alpha) - (alpha + 1) log D
+      TEB block, inverse-Wishart(Psi, nu = n_b - 3), det = TT EE - TE^2:
+        TT column (kind 2, arg = |Psi|): coef = nu / 2, Y = EE / (2 det)
+        EE column (kind 0): Y = TT / (2 det);  TE column (kind 0): Y = -TE / det
+        cst += -nu log 2 - logGamma_2(nu / 2) - (n_b / 2) log det,
+        logGamma_2(x) = log(pi) / 2 + lgamma(x) + lgamma(x - 1 / 2)."""
+    F = int(nfields)
+    spectra = SPECTRA[F]
+    theory = np.asarray(theory, dtype=np.float64)
+    mask = np.asarray(mask, dtype=bool)
+    if theory.ndim != 3 or theory.shape[1:] != mask.shape or mask.shape[0] != len(spectra):
+        raise ValueError("br_likelihood_tables: theory must be [K, nspec, maxbins] and mask [nspec, maxbins]")
+    K, nspec, maxbins = theory.shape
+    used = mask & br_likelihood_mask(F, bins, maxbins)
+    block = (0, 1, 3) if F == 3 else ()
+    for k in block[1:]:
+        used[k] = used[0]
+    Ju = int(used.sum())
+    cols = np.flatnonzero(used.reshape(-1)).astype(np.int32)
+    kind = np.zeros(Ju, dtype=np.int32)
+    coef = np.zeros(Ju)
+    Y = np.zeros((K, Ju))
+    cst = [[] for _ in range(K)]
+    pos = {int(c): j for j, c in enumerate(cols)}
+    with np.errstate(all="ignore"):
+        for sp, s in enumerate(spectra):
+            if sp in block[1:]:
+                continue
+            e = np.asarray(bins[s], dtype=np.float64)
+            for b in np.flatnonzero(used[sp]):
+                n_b = e[b + 1] ** 2 - e[b] ** 2
+                j = pos[sp * maxbins + int(b)]
+                if sp in block:
+                    nu = n_b - 3.0
+                    tt, ee, te = theory[:, 0, b], theory[:, 1, b], theory[:, 3, b]
+                    det = tt * ee - te * te
+                    kind[j], coef[j] = 2, 0.5 * nu
+                    Y[:, j] = 0.5 * ee / det
+                    Y[:, pos[maxbins + int(b)]] = 0.5 * tt / det
+                    Y[:, pos[3 * maxbins + int(b)]] = -te / det
+                    lg2 = 0.5 * math.log(math.pi) + math.lgamma(0.5 * nu) + math.lgamma(0.5 * nu - 0.5)
+                    term = -nu * math.log(2.0) - lg2 - 0.5 * n_b * np.log(det)
+                else:
+                    alpha = 0.5 * n_b - 1.0
+                    D = theory[:, sp, b]
+                    kind[j], coef[j] = 1, alpha
+                    Y[:, j] = 1.0 / D
+                    term = -math.lgamma(alpha) - (alpha + 1.0) * np.log(D)
+                for k in range(K):
+                    cst[k].append(float(term[k]))
+    return {"cols": cols, "kind": kind, "coef": coef, "Y": Y, "cst": np.array([math.fsum(v) for v in cst])}
+
+
+class BlackwellRaoLikelihood:
+    """Streaming Blackwell-Rao likelihood of K theory spectra over the gs_brl_*
+    C-ABI (gs_brl.hip documents the state and the order of operations): a flat
+    fp64 device tensor ``data`` = 8 header doubles (int64 iteration count
+    first), the planes m, S, Q [3, nchains, K] and the int64 counts of skipped
+    rows [nchains].  tables: br_likelihood_tables' dict (kept on the device).
+    Plan-independent: any scale ring [capacity, nchains, nspec, maxbins] can be
+    accumulated."""
+    HDR = 8
+    TABLES = ("cols", "kind", "coef", "Y", "cst")
+
+    def __init__(self, nchains, nspec, maxbins, tables, device=None, data=None):
+        _require_gpu()
+        self.lib = C.load()
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+        self.nchains, self.nspec, self.maxbins = int(nchains), int(nspec), int(maxbins)
+        host = {k: torch.as_tensor(tables[k]).cpu() for k in self.TABLES}
+        cols, kind = host["cols"].to(torch.int64), host["kind"].to(torch.int64)
+        self.Ju = int(cols.numel())
+        nsb = self.nspec * self.maxbins
+        if host["Y"].dim() != 2 or self.Ju < 1 or host["Y"].shape[1] != self.Ju or kind.numel() != self.Ju or \
+                host["coef"].numel() != self.Ju or host["cst"].numel() != host["Y"].shape[0]:
+            raise ValueError("Blackwell-Rao likelihood: tables must be cols, kind, coef [Ju], Y [K, Ju] and cst [K]")
+        # what the kernel indexes the ring with
+        if int(cols.min()) < 0 or int(cols.max()) >= nsb or (self.Ju > 1 and bool((cols[1:] <= cols[:-1]).any())):
+            raise ValueError("Blackwell-Rao likelihood: cols must ascend within [0, nspec * maxbins)")
+        if bool(((kind < 0) | (kind > 2)).any()) or bool((cols[kind == 2] + 3 * self.maxbins >= nsb).any()):
+            raise ValueError("Blackwell-Rao likelihood: kind must be 0, 1 or 2 (2: a TT column of four spectra)")
+        self.K = int(host["Y"].shape[0])
+        self.cols = host["cols"].to(torch.int32).to(dev).contiguous()
+        self.kind = host["kind"].to(torch.int32).to(dev).contiguous()
+        self.coef, self.Y, self.cst = (host[k].to(torch.float64).to(dev).contiguous() for k in ("coef", "Y", "cst"))
+        nb = ctypes.c_longlong()
+        C.check(self.lib.gs_brl_bytes(self.nchains, self.K, ctypes.byref(nb)), "gs_brl_bytes")
+        if data is None:
+            self.data = torch.zeros(nb.value // 8, dtype=torch.float64, device=dev)
+        else:
+            self.data = torch.as_tensor(data, dtype=torch.float64).to(dev).contiguous().clone()
+            if self.data.numel() * 8 != nb.value:
+                raise ValueError("Blackwell-Rao likelihood state: size does not match its dimensions")
+
+    def tables(self):
+        """The tables as host tensors (what a state_dict carries)."""
+        return {k: getattr(self, k).cpu().clone() for k in self.TABLES}
+
+    def reset(self):
+        C.check(self.lib.gs_brl_reset(C.ptr(self.data), self.nchains, self.K, C.stream_ptr()), "gs_brl_reset")
+
+    def update(self, scales, capacity, first_iteration, nsteps):
+        """Add iterations first_iteration .. first_iteration + nsteps - 1 from the
+        scale ring (iteration it in slot (it - 1) % capacity)."""
+        if scales.numel() < int(capacity) * self.nchains * self.nspec * self.maxbins:
+            raise ValueError("Blackwell-Rao likelihood update: the scale ring is smaller than capacity rows")
+        C.check(self.lib.gs_brl_update(C.ptr(self.data), self.nchains, self.nspec, self.maxbins, self.K, self.Ju,
+                                       C.ptr(self.cols), C.ptr(self.kind), C.ptr(self.coef), C.ptr(self.Y),
+                                       C.ptr(scales), int(capacity), int(first_iteration), int(nsteps),
+                                       C.stream_ptr()), "gs_brl_update")
+
+    @property
+    def n(self):
+        """Iterations added (reads the device count: synchronises)."""
+        return int(self.data[:1].view(torch.int64).item())
+
+    def fields(self):
+        """The planes m, S and Q as a view [3, nchains, K]."""
+        return self.data[self.HDR:self.HDR + 3 * self.nchains * self.K].view(3, self.nchains, self.K)
+
+    def bad(self):
+        """int64 [nchains]: rows skipped for a scale or a block determinant <= 0 or
+        not finite (a view)."""
+        return self.data[self.HDR + 3 * self.nchains * self.K:].view(torch.int64)
+
+    def finish(self, gather=None):
+        """Device tensors loglike [K], chain_loglike [C, K] and neff [K], and n.
+        gather (ShardContext.gather): the planes are all-gathered along the
+        chain axis first and the finish runs over every rank's chains."""
+        data, nch = self.data, self.nchains
+        if gather is not None:
+            body = gather(self.fields().contiguous(), dim=1)
+            nch = int(body.shape[1])
+            data = torch.cat([self.data[:self.HDR], body.reshape(-1)])
+        dev = self.data.device
+        loglike = torch.zeros(self.K, dtype=torch.float64, device=dev)
+        chain = torch.zeros(nch, self.K, dtype=torch.float64, device=dev)
+        neff = torch.zeros(self.K, dtype=torch.float64, device=dev)
+        C.check(self.lib.gs_brl_finish(C.ptr(data), nch, self.K, C.ptr(self.cst), C.ptr(loglike), C.ptr(chain),
+                                       C.ptr(neff), C.stream_ptr()), "gs_brl_finish")
+        return {"loglike": loglike, "chain_loglike": chain, "neff": neff, "n": self.n}
+
+
 def stats_layout(F):
     """Names of the statistic rows (include/gibbs_capi.h GS_NSTAT_*)."""
     return {1: ["ssTT", "dTsT"], 2: ["ssEE", "ssBB", "dEsE", "dBsB"],

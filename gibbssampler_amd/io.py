@@ -334,14 +334,17 @@ def write_map(filename, m, nest=False, dtype=np.float32, column_names=None, over
 def run_record(h_cls, h_accept_cr, h_duration_cr, bins, blocks, proposal_variances, total_time, total_cpu_time,
                pcg_accuracy=None, rj_step=False, gibbs_iterations=None, gibbs_cr=False, h_accept_nc=None,
                h_duration_cls_centered=None, h_duration_cls_non_centered=None, h_duration_iteration=None,
-               tuned_proposal_variances=None, n_warmup=None, blackwell_rao=None, h_scales=None):
+               tuned_proposal_variances=None, n_warmup=None, blackwell_rao=None, h_scales=None,
+               br_likelihood=None):
     """the dict main_polarization.py:172-181 builds (same keys; the reference
     stores h_accept_cr under both h_accept_nc and h_accept_cr).  A run that
     adapted its proposal scales (n_warmup > 0) also stores the tuned variances
     next to the given ones: tuned_proposal_variances_<spectrum>, n_warmup.
     blackwell_rao (a sampler's blackwell_rao_posterior) is stored per spectrum
     as blackwell_rao_<spectrum> = {grid, logpdf, mass, alpha, n}, and h_scales
-    (the scale history of keep_scales=True) under h_scales."""
+    (the scale history of keep_scales=True) under h_scales.  br_likelihood (a
+    sampler's blackwell_rao_likelihood) is stored under br_likelihood =
+    {loglike, chain_loglike, neff, n, bad}."""
     rec = {"h_cls": h_cls, "h_accept_nc": h_accept_cr if h_accept_nc is None else h_accept_nc,
             "h_duration_cls_centered": h_duration_cls_centered, "h_duration_cr": h_duration_cr,
             "bins_EE": bins["EE"], "bins_BB": bins["BB"], "blocks_EE": blocks["EE"],
@@ -360,6 +363,8 @@ def run_record(h_cls, h_accept_cr, h_duration_cr, bins, blocks, proposal_varianc
             rec["blackwell_rao_" + s] = {k: v[k] for k in ("grid", "logpdf", "mass", "alpha", "n")}
     if h_scales is not None:
         rec["h_scales"] = h_scales
+    if br_likelihood is not None:
+        rec["br_likelihood"] = {k: br_likelihood[k] for k in ("loglike", "chain_loglike", "neff", "n", "bad")}
     return rec
 
 

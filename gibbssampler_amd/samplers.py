@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from . import _capi as C
-from .engine import BlackwellRaoState, GibbsPlan, MH_ORDER, SummaryState
+from .engine import BlackwellRaoLikelihood, BlackwellRaoState, GibbsPlan, MH_ORDER, SummaryState
 
 INIT_ITER = 0xFFFFFFFF
 ADAPT_KAPPA = 0.6       # Robbins-Monro step n^-kappa of the warm-up adaptation
@@ -127,6 +127,85 @@ def check_blackwell_rao(br, nfields, bins, dls_init=None, maxbins=None):
     return {"grid": grid, "alpha": alpha, "half_mask": half, "start": None if start is None else int(start)}
 
 
+def check_br_likelihood(opts, nfields, bins, maxbins=None):
+    """run(br_likelihood=...): None / False (off) or {"theory": {spectrum: [K,
+    nbins]} or an array [K, nspec, maxbins], "lrange": (lmin, lmax) or "mask":
+    bool [nspec, maxbins] or {spectrum: [nbins]} (default: every drawn bin),
+    "start": as the summary's}.  Returns None or {tables, mask, K, start}
+    (tables: engine.br_likelihood_tables)."""
+    from .engine import SPECTRA, br_likelihood_mask, br_likelihood_tables
+    if opts is None or opts is False:
+        return None
+    if not isinstance(opts, dict) or "theory" not in opts:
+        raise ValueError("br_likelihood: a dict {theory[, lrange | mask][, start]} is needed")
+    bad = set(opts) - {"theory", "lrange", "mask", "start"}
+    if bad:
+        raise ValueError(f"br_likelihood: unknown options {sorted(bad)}")
+    if "lrange" in opts and "mask" in opts:
+        raise ValueError("br_likelihood: give either lrange or mask")
+    start = opts.get("start")
+    if start is not None and int(start) < 0:
+        raise ValueError("br_likelihood: start must be >= 0")
+    F = int(nfields)
+    spectra = SPECTRA[F]
+    drawn = br_likelihood_mask(F, bins, maxbins)
+    nspec, maxbins = drawn.shape
+    th = opts["theory"]
+    if isinstance(th, dict):
+        if set(th) != set(spectra):
+            raise ValueError(f"br_likelihood: theory needs the spectra {list(spectra)}")
+        rows = [np.atleast_2d(np.asarray(th[s], dtype=np.float64)) for s in spectra]
+        K = rows[0].shape[0]
+        theory = np.ones((K, nspec, maxbins))
+        for k, (s, v) in enumerate(zip(spectra, rows)):
+            nb = len(bins[s]) - 1
+            if v.ndim != 2 or v.shape != (K, nb):
+                raise ValueError(f"br_likelihood: theory[{s}] must be [K, nbins] = [{K}, {nb}]")
+            theory[:, k, :nb] = v
+    else:
+        theory = np.array(th, dtype=np.float64)
+        if theory.ndim != 3 or theory.shape[1:] != (nspec, maxbins):
+            raise ValueError(f"br_likelihood: theory must be [K, nspec, maxbins] = [K, {nspec}, {maxbins}]")
+    K = theory.shape[0]
+    if K < 1:
+        raise ValueError("br_likelihood: at least one theory spectrum (K >= 1) is needed")
+    if "mask" in opts:
+        mk = opts["mask"]
+        if isinstance(mk, dict):
+            mask = np.zeros((nspec, maxbins), dtype=bool)
+            for k, s in enumerate(spectra):
+                v = np.asarray(mk[s], dtype=bool)
+                mask[k, :len(v)] = v
+        else:
+            mask = np.array(mk, dtype=bool)
+            if mask.shape != (nspec, maxbins):
+                raise ValueError(f"br_likelihood: mask must be [nspec, maxbins] = [{nspec}, {maxbins}]")
+        mask &= drawn
+    else:
+        lr = opts.get("lrange")
+        if lr is not None and not (len(lr) == 2 and lr[0] <= lr[1]):
+            raise ValueError("br_likelihood: lrange must be (lmin, lmax) with lmin <= lmax")
+        mask = br_likelihood_mask(F, bins, maxbins, lr)
+    if F == 3 and not (np.array_equal(mask[0], mask[1]) and np.array_equal(mask[0], mask[3])):
+        raise ValueError("br_likelihood: the TEB block is used as a whole: the mask of TT, EE and TE must agree")
+    if not mask.any():
+        raise ValueError("br_likelihood: no bin is used (empty used set)")
+    pos = mask.copy()                       # every used spectrum but TE is a variance
+    if F == 3:
+        pos[3] = False
+    tp = theory[:, pos]
+    if not (np.all(np.isfinite(theory[:, mask])) and np.all(tp > 0)):
+        raise ValueError("br_likelihood: theory values must be finite, and positive but for TE, on the used bins")
+    if F == 3:
+        m0 = mask[0]
+        det = theory[:, 0, m0] * theory[:, 1, m0] - theory[:, 3, m0] ** 2
+        if not np.all(det > 0):
+            raise ValueError("br_likelihood: a used TEB block of the theory must be positive definite "
+                             "(det = TT EE - TE^2 > 0)")
+    return {"tables": br_likelihood_tables(F, bins, theory, mask), "mask": mask, "K": K,
+            "start": None if start is None else int(start)}
+
+
 def warmup_of_state(st):
     """(n_warmup, target_accept, log_scale, count) of a state_dict(); states
     written before the adaptation existed (no such keys) are 'not adapting'."""
@@ -212,6 +291,10 @@ class BatchedRunner:
         self._br = None
         self.br_start = 0
         self.h_scales = None
+        # streaming Blackwell-Rao likelihood of theory spectra (run(br_likelihood=...)):
+        # the device state with its tables and the iteration after which it accumulates
+        self._brl = None
+        self.brl_start = 0
 
     def __del__(self):
         # dropped inside another sampler's capture: keep the kept hipGraphs, the
@@ -279,6 +362,10 @@ class BatchedRunner:
             br = self._br
             st.update(br_state=br.data.cpu().clone(), br_grid=br.grid.cpu().clone(), br_alpha=br.alpha.cpu().clone(),
                       br_half_mask=int(br.half_mask), br_start=int(self.br_start))
+        if self._brl is not None:
+            bl = self._brl
+            st.update(brl_state=bl.data.cpu().clone(), brl_start=int(self.brl_start),
+                      **{"brl_" + k: v for k, v in bl.tables().items()})
         if self.rng == "replay":
             name, keys, pos, has_gauss, cached = np.random.get_state()
             st.update(numpy_rng_keys=torch.from_numpy(np.asarray(keys, dtype=np.int64)), numpy_rng_pos=int(pos),
@@ -331,6 +418,14 @@ class BatchedRunner:
             self.br_start = int(st["br_start"])
         else:
             self._br = None
+        # and one without the likelihood's keys
+        if st.get("brl_state") is not None:
+            self._brl = BlackwellRaoLikelihood(p.nchains, p.nspec, p.maxbins,
+                                               {k: st["brl_" + k] for k in BlackwellRaoLikelihood.TABLES},
+                                               device=p.device, data=st["brl_state"])
+            self.brl_start = int(st["brl_start"])
+        else:
+            self._brl = None
         if self.rng == "replay" and "numpy_rng_keys" in st:
             np.random.set_state(("MT19937", st["numpy_rng_keys"].numpy().astype(np.uint32), st["numpy_rng_pos"],
                                  st["numpy_rng_has_gauss"], st["numpy_rng_cached"]))
@@ -470,6 +565,28 @@ class BatchedRunner:
                       "alpha": alpha[i, :nb].copy(), "n": out["n"], "bad": int(bad[:, i].sum())}
         return res
 
+    # -- streaming Blackwell-Rao likelihood -----------------------------------------------
+    def _brl_update(self, scales, capacity, it0, k):
+        """As _br_update, for the likelihood state and brl_start."""
+        first = max(it0, self.brl_start) + 1
+        n = it0 + k - first + 1
+        if n > 0:
+            self._brl.update(scales, capacity, first, n)
+
+    def br_likelihood(self, gather=None):
+        """The Blackwell-Rao likelihood of the theory spectra of the last
+        run(br_likelihood=...), numpy: loglike [K] = log L(D^th_k | d) over all
+        chains, chain_loglike [C, K] (each chain's own estimate), neff [K] (the
+        effective number of samples that carry the estimate, in [1, C n]), n,
+        the iterations per chain, and bad [chains of this rank], the rows
+        skipped for a non-positive or non-finite scale.  gather as in summary()."""
+        if self._brl is None:
+            raise RuntimeError("br_likelihood: the last run() kept no likelihood state (run(br_likelihood=...))")
+        out = self._brl.finish(gather if gather is not None else self._gather)
+        res = {k: out[k].cpu().numpy() for k in ("loglike", "chain_loglike", "neff")}
+        res.update(n=out["n"], bad=self._brl.bad().cpu().numpy().copy())
+        return res
+
     def summary_accept_counts(self, gather=None):
         """(counts per spectrum {s: int64 [chains, flags]}, n) of the summarised
         iterations (None for the centered sampler)."""
@@ -578,7 +695,8 @@ class BatchedRunner:
 
     # -- a whole run --------------------------------------------------------------------
     def run(self, dls_init, n_iter, timings=False, gather=None, graph_chunk=32, resume=None, n_warmup=0,
-            target_accept=0.25, summary=None, keep_history=True, blackwell_rao=None, keep_scales=False):
+            target_accept=0.25, summary=None, keep_history=True, blackwell_rao=None, keep_scales=False,
+            br_likelihood=None):
         """n_iter iterations from dls_init; returns (histories, accepts[, step
         times]).  gather: ShardContext.gather of a torchrun job -- the device
         histories of every rank are all-gathered along the chain axis (global
@@ -610,14 +728,27 @@ class BatchedRunner:
         It also lifts the need for a summary of keep_history=False.  A resumed
         state that carries one continues it.  keep_scales: keep the scale history
         {spectrum: [n_iter, chains, nbins]} in runner.h_scales (row i belongs to
-        the run's iteration i + 1; the start has no scale)."""
+        the run's iteration i + 1; the start has no scale).
+        br_likelihood: None or {"theory": {spectrum: [K, nbins]} or [K, nspec,
+        maxbins], "lrange": (lmin, lmax) or "mask": ..., "start": ...} -- the
+        streaming Blackwell-Rao likelihood of K fixed theory spectra over the
+        used bins (runner.br_likelihood()): the joint inverse-Gamma /
+        inverse-Wishart density of the theory under every sample's conditional,
+        accumulated from the same scale ring after every chunk replay / eager
+        step into 24 B per (chain, model).  Centered and ASIS only; it too
+        lifts the need for a summary of keep_history=False, and a resumed
+        state that carries one continues it."""
         p = self.plan
         n_warmup = check_warmup(self.kind, self.rng, n_warmup, target_accept)
         br_opts = check_blackwell_rao(blackwell_rao, p.F, p.bins, dls_init, p.maxbins)
+        brl_opts = check_br_likelihood(br_likelihood, p.F, p.bins, p.maxbins)
         if (br_opts is not None or keep_scales) and self.kind == "noncentered":
             raise NotImplementedError("blackwell_rao / keep_scales: the non-centered sampler has no centered "
                                       "conditional draw (use the centered or the ASIS sampler)")
-        sm_opts = check_summary(summary, keep_history or br_opts is not None)
+        if brl_opts is not None and self.kind == "noncentered":
+            raise NotImplementedError("br_likelihood: the non-centered sampler has no centered conditional draw "
+                                      "(use the centered or the ASIS sampler)")
+        sm_opts = check_summary(summary, keep_history or br_opts is not None or brl_opts is not None)
         if p.scale_trace is not None:
             p.cls_scale_trace(None)         # left attached by a run that raised
         self._gather = gather
@@ -649,12 +780,20 @@ class BatchedRunner:
                 self._br = BlackwellRaoState(p.nchains, br_opts["grid"], br_opts["alpha"], br_opts["half_mask"],
                                              device=p.device)
                 self.br_start = self.n_warmup if br_opts["start"] is None else br_opts["start"]
-        sm, br = self._summary, self._br
+        if resume is None or self._brl is None:
+            if brl_opts is None:
+                self._brl = None
+            else:
+                self._brl = BlackwellRaoLikelihood(p.nchains, p.nspec, p.maxbins, brl_opts["tables"], device=p.device)
+                self.brl_start = self.n_warmup if brl_opts["start"] is None else brl_opts["start"]
+        sm, br, brl = self._summary, self._br, self._brl
         if br is not None and self.kind == "noncentered":
             raise NotImplementedError("blackwell_rao: the non-centered sampler has no centered conditional draw")
-        if sm is None and br is None and not keep_history:
+        if brl is not None and self.kind == "noncentered":
+            raise NotImplementedError("br_likelihood: the non-centered sampler has no centered conditional draw")
+        if sm is None and br is None and brl is None and not keep_history:
             raise ValueError("keep_history=False needs a summary")
-        with_scales = br is not None or keep_scales
+        with_scales = br is not None or brl is not None or keep_scales
         self.h_scales = None
         Hs = p.zeros(n_iter, p.nchains, p.nspec, p.maxbins) if keep_scales else None
         # steps of this run that adapt; warm-up and frozen steps never share a graph
@@ -723,6 +862,8 @@ class BatchedRunner:
                     self._summary_update(trace, chunk, self.iteration - k, k, acc_tr, acc_tr.stride(0))
                 if br is not None:
                     self._br_update(sc_tr, chunk, self.iteration - k, k)
+                if brl is not None:
+                    self._brl_update(sc_tr, chunk, self.iteration - k, k)
                 if keep_scales:
                     Hs[done:done + k].copy_(sc_tr[:k] if r0 == 0 else sc_tr[(torch.arange(k) + r0) % chunk])
                 h0, h1 = (0 if done == 0 else off + done), off + done + k
@@ -773,6 +914,8 @@ class BatchedRunner:
                 p.mh_adapt(self.accept)
             if br is not None:
                 self._br_update(sc1, 1, self.iteration - 1, 1)
+            if brl is not None:
+                self._brl_update(sc1, 1, self.iteration - 1, 1)
             if keep_scales:
                 Hs[i].copy_(sc1[0])
             if sm is not None:

@@ -397,6 +397,45 @@ int gs_br_update(void* state, int nchains, int nspec, int maxbins, int G, const 
 int gs_br_finish(const void* state, int C, int nspec, int maxbins, int G, const double* grid, const double* alpha,
                  double* logpdf, double* mass, void* stream);
 
+/* ---- streaming Blackwell-Rao likelihood of theory spectra (gs_brl.hip) ---------
+ * The joint Blackwell-Rao estimate (Chu et al. 2005) for K fixed theory spectra,
+ *   L(D^th_k | d) ~ 1/(C n) sum_{c,i} prod_b P(D^th_k,b | s_c,i),
+ * P the inverse-Gamma density of an independent bin and the 2x2 inverse-Wishart
+ * density of a TEB block (TT, EE, TE).  With x the row of the scale ring
+ * [capacity][nchains][nspec][maxbins] (gs_cls_scale_trace) of one (iteration,
+ * chain) and j over the Ju used columns, the log density up to a per-model
+ * constant is t = r - sum_j x_j Y_kj with r = sum_j coef_j log(arg_j).  DEVICE
+ * tables (built by the host, engine.br_likelihood_tables):
+ *   cols [Ju] int32  ascending used columns (spectrum * maxbins + bin); the
+ *                    other columns of the ring are never read
+ *   kind [Ju] int32  0: no logarithm; 1: arg = x; 2: the TT column of a TEB
+ *                    block, arg = x * x[col + maxbins] - x[col + 3 maxbins]^2
+ *   coef [Ju] fp64   alpha_b (kind 1), nu_b / 2 (kind 2)
+ *   Y    [K][Ju] fp64
+ * The state is a caller-owned DEVICE buffer of gs_brl_bytes bytes: 8 header
+ * doubles (int64 iteration count first), the planes m, S, Q [nchains][K] (24 B
+ * per chain and model: running maximum of t, sum exp(t - m), sum exp(2 (t -
+ * m))) and int64 bad [nchains], the rows skipped for a chain because a kind 1
+ * value or a kind 2 determinant was <= 0 or not finite.  gs_brl_reset zeroes it.
+ * gs_brl_update adds iterations first_iteration ... first_iteration + nsteps - 1
+ * (iteration it in slot (it - 1) % capacity; nsteps <= capacity) in one launch;
+ * every dot product is one fma chain over j ascending and every (chain, model)
+ * is folded in iteration order, so the state's bits do not depend on how the
+ * iterations were cut into launches, on the chain count or on K.  Successive
+ * updates of one state must be ordered on one stream.
+ * gs_brl_finish over the C chains of a state (planes all-gathered along the
+ * chain axis: every rank's chains), cst [K] the models' constants (DEVICE):
+ *   loglike [K], chain_loglike [C][K] (one chain's own estimate), neff [K] =
+ *   (sum w)^2 / sum w^2 over the samples' weights, in [1, C n].
+ * gs_brl.hip documents the layout and the order of every operation. */
+int gs_brl_bytes(int nchains, int K, long long* bytes /* HOST */);
+int gs_brl_reset(void* state, int nchains, int K, void* stream);
+int gs_brl_update(void* state, int nchains, int nspec, int maxbins, int K, int Ju, const int* cols, const int* kind,
+                  const double* coef, const double* Y, const double* scales, int capacity, uint32_t first_iteration,
+                  int nsteps, void* stream);
+int gs_brl_finish(const void* state, int C, int K, const double* cst, double* loglike, double* chain_loglike,
+                  double* neff, void* stream);
+
 /* device-side timing of the dominant kernel: with enable = 1 every later CR-sweep
  * launch is bracketed by hipEvents on its stream (also while the stream is
  * captured into a hipGraph: external event-record nodes, timed at each replay);
