@@ -139,6 +139,11 @@ _SIGS = [
     ("gs_brl_update", ctypes.c_int, [_VP] + [ctypes.c_int] * 5 + [_VP] * 5 + [ctypes.c_int, ctypes.c_uint32,
                                                                             ctypes.c_int, _VP]),
     ("gs_brl_finish", ctypes.c_int, [_VP] + [ctypes.c_int] * 2 + [_VP] * 5),
+    ("gs_brs_info", ctypes.c_int, [c_int_p, c_int_p]),
+    ("gs_brs_work_bytes", ctypes.c_int, [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_longlong)]),
+    ("gs_brs_append", ctypes.c_int, [_VP, _VP] + [ctypes.c_int] * 5 + [_VP] * 4 + [ctypes.c_int, ctypes.c_uint32,
+                                                                                ctypes.c_int, ctypes.c_int, _VP]),
+    ("gs_brs_eval", ctypes.c_int, [_VP, _VP] + [ctypes.c_int] * 5 + [_VP, _VP, ctypes.c_longlong, _VP, _VP]),
     ("gs_sht_create", ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(_VP)]),
     ("gs_sht_destroy", ctypes.c_int, [_VP]),
     ("gs_sht_info", ctypes.c_int, [_VP, c_int_p, c_int_p, ctypes.POINTER(ctypes.c_longlong),

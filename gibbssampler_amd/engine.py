@@ -740,6 +740,177 @@ class BlackwellRaoLikelihood:
         return {"loglike": loglike, "chain_loglike": chain, "neff": neff, "n": self.n}
 
 
+class BlackwellRaoSamples:
+    """Blackwell-Rao sample bank over the gs_brs_* C-ABI (gs_brs.hip documents the
+    layout and the order of operations): the scales of the used bins of every
+    kept sample, X [nchains, capacity, Jp] and r [nchains, capacity] on the
+    device, filled from a scale ring during a run (append) and scored against
+    any theory spectra afterwards (loglike) -- the theory need not be known
+    before the run, unlike BlackwellRaoLikelihood's.  mask: bool [nspec,
+    maxbins], the used bins (the TEB block as a whole).  The tables cols, kind
+    and coef are those of br_likelihood_tables; they do not depend on a theory."""
+    HDR = 8
+
+    def __init__(self, nchains, nfields, bins, mask, capacity, device=None):
+        _require_gpu()
+        self.lib = C.load()
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+        self.nchains, self.nfields = int(nchains), int(nfields)
+        spectra = SPECTRA[self.nfields]
+        self.bins = {s: np.asarray(bins[s], dtype=np.int64).copy() for s in spectra}
+        self.mask = np.array(mask, dtype=bool)
+        if self.mask.ndim != 2 or self.mask.shape[0] != len(spectra):
+            raise ValueError("Blackwell-Rao sample bank: mask must be bool [nspec, maxbins]")
+        self.nspec, self.maxbins = self.mask.shape
+        one = np.ones((1, self.nspec, self.maxbins))
+        if self.nfields == 3:
+            one[:, 3] = 0.0
+        tab = br_likelihood_tables(self.nfields, self.bins, one, self.mask)
+        self.Ju = int(len(tab["cols"]))
+        if self.Ju < 1:
+            raise ValueError("Blackwell-Rao sample bank: no bin is used (empty used set)")
+        self.Jp = (self.Ju + 3) // 4 * 4
+        self.cols = torch.from_numpy(tab["cols"]).to(torch.int32).to(self.device).contiguous()
+        self.kind = torch.from_numpy(tab["kind"]).to(torch.int32).to(self.device).contiguous()
+        self.coef = torch.from_numpy(tab["coef"]).to(torch.float64).to(self.device).contiguous()
+        sl, tm = ctypes.c_int(), ctypes.c_int()
+        C.check(self.lib.gs_brs_info(ctypes.byref(sl), ctypes.byref(tm)), "gs_brs_info")
+        self.slice_rows, self.model_tile = sl.value, tm.value
+        self.capacity = 0
+        self._n = 0
+        self.X = self.r = None
+        self.reserve(max(int(capacity), 1))
+
+    def nbytes(self, capacity):
+        """Device bytes of a bank of `capacity` rows per chain."""
+        return 8 * self.nchains * int(capacity) * (self.Jp + 1)
+
+    def reserve(self, capacity):
+        """Grow the bank to `capacity` rows per chain (rows [0, n) are kept)."""
+        capacity = int(capacity)
+        if capacity <= self.capacity:
+            return
+        if self.nchains * capacity > 2 ** 31 - 1:
+            raise ValueError("Blackwell-Rao sample bank: nchains * capacity exceeds 2^31 - 1 rows")
+        need = self.nbytes(capacity)
+        free = torch.cuda.mem_get_info(self.device)[0]
+        if need > free:
+            raise RuntimeError(f"Blackwell-Rao sample bank: {need} bytes ({self.nchains} chains x {capacity} rows x "
+                               f"{self.Jp + 1} values) do not fit in the {free} bytes of free device memory")
+        X = torch.zeros(self.nchains, capacity, self.Jp, dtype=torch.float64, device=self.device)
+        r = torch.zeros(self.nchains, capacity, dtype=torch.float64, device=self.device)
+        if self._n:
+            X[:, :self._n].copy_(self.X[:, :self._n])
+            r[:, :self._n].copy_(self.r[:, :self._n])
+        self.X, self.r, self.capacity = X, r, capacity
+
+    @property
+    def n(self):
+        """Rows (kept samples per chain) in the bank."""
+        return self._n
+
+    def append(self, scales, ring_capacity, first_iteration, nsteps):
+        """Append iterations first_iteration .. first_iteration + nsteps - 1 of the
+        scale ring (iteration it in slot (it - 1) % ring_capacity) at rows n .."""
+        if scales.numel() < int(ring_capacity) * self.nchains * self.nspec * self.maxbins:
+            raise ValueError("Blackwell-Rao sample bank append: the scale ring is smaller than ring_capacity rows")
+        C.check(self.lib.gs_brs_append(C.ptr(self.X), C.ptr(self.r), self.nchains, self.capacity, self.Ju, self.nspec,
+                                       self.maxbins, C.ptr(self.cols), C.ptr(self.kind), C.ptr(self.coef),
+                                       C.ptr(scales), int(ring_capacity), int(first_iteration), int(nsteps), self._n,
+                                       C.stream_ptr()), "gs_brs_append")
+        self._n += int(nsteps)
+
+    def tables(self, theory):
+        """br_likelihood_tables of a theory ({spectrum: [K, nbins]} or [K, nspec,
+        maxbins]; checked as run(br_likelihood=)'s) with the bank's mask."""
+        from .samplers import br_theory
+        th = br_theory("Blackwell-Rao sample bank", theory, self.nfields, self.bins, self.mask)
+        return br_likelihood_tables(self.nfields, self.bins, th, self.mask)
+
+    def evaluate(self, Y):
+        """The gs_brl state (header, m, S, Q [nchains, K], bad [nchains]) of Y [K,
+        Ju] over rows [0, n): a flat fp64 device tensor."""
+        Y = torch.as_tensor(Y, dtype=torch.float64).to(self.device).contiguous()
+        if Y.dim() != 2 or Y.shape[1] != self.Ju or Y.shape[0] < 1:
+            raise ValueError(f"Blackwell-Rao sample bank: Y must be [K, Ju] = [K, {self.Ju}]")
+        K = int(Y.shape[0])
+        nb, wb = ctypes.c_longlong(), ctypes.c_longlong()
+        C.check(self.lib.gs_brl_bytes(self.nchains, K, ctypes.byref(nb)), "gs_brl_bytes")
+        C.check(self.lib.gs_brs_work_bytes(self.nchains, self._n, K, ctypes.byref(wb)), "gs_brs_work_bytes")
+        state = torch.empty(nb.value // 8, dtype=torch.float64, device=self.device)
+        work = torch.empty(wb.value // 8, dtype=torch.float64, device=self.device)
+        C.check(self.lib.gs_brs_eval(C.ptr(self.X), C.ptr(self.r), self.nchains, self.capacity, self._n, self.Ju, K,
+                                     C.ptr(Y), C.ptr(work), wb.value, C.ptr(state), C.stream_ptr()), "gs_brs_eval")
+        return state
+
+    def fields(self, state):
+        """The planes m, S and Q of an evaluate() state as a view [3, nchains, K]."""
+        K = (state.numel() - self.HDR - self.nchains) // (3 * self.nchains)
+        return state[self.HDR:self.HDR + 3 * self.nchains * K].view(3, self.nchains, K)
+
+    def loglike(self, theory, gather=None):
+        """The Blackwell-Rao likelihood of K theory spectra over the bank, numpy:
+        {loglike [K], chain_loglike [C, K], neff [K], n, bad [nchains]} as
+        runner.br_likelihood() gives them.  gather (ShardContext.gather): the
+        state planes are all-gathered along the chain axis before the finish."""
+        tab = self.tables(theory)
+        K = int(tab["Y"].shape[0])
+        state = self.evaluate(tab["Y"])
+        cst = torch.from_numpy(np.ascontiguousarray(tab["cst"])).to(self.device)
+        bad = state[self.HDR + 3 * self.nchains * K:].view(torch.int64).cpu().numpy().copy()
+        nch = self.nchains
+        if gather is not None:
+            body = gather(self.fields(state).contiguous(), dim=1)
+            nch = int(body.shape[1])
+            state = torch.cat([state[:self.HDR], body.reshape(-1)])
+        loglike = torch.zeros(K, dtype=torch.float64, device=self.device)
+        chain = torch.zeros(nch, K, dtype=torch.float64, device=self.device)
+        neff = torch.zeros(K, dtype=torch.float64, device=self.device)
+        C.check(self.lib.gs_brl_finish(C.ptr(state), nch, K, C.ptr(cst), C.ptr(loglike), C.ptr(chain), C.ptr(neff),
+                                       C.stream_ptr()), "gs_brl_finish")
+        return {"loglike": loglike.cpu().numpy(), "chain_loglike": chain.cpu().numpy(), "neff": neff.cpu().numpy(),
+                "n": self._n, "bad": bad}
+
+    # -- checkpoints and files -------------------------------------------------------
+    def state(self):
+        """Host tensors of rows [0, n) and the mask (what a state_dict carries)."""
+        return {"X": self.X[:, :self._n].cpu().clone(), "r": self.r[:, :self._n].cpu().clone(),
+                "mask": torch.from_numpy(self.mask.copy())}
+
+    @classmethod
+    def from_state(cls, st, nfields, bins, capacity=None, device=None):
+        """A bank holding the rows of state() (capacity: rows to make room for)."""
+        X, r = torch.as_tensor(st["X"], dtype=torch.float64), torch.as_tensor(st["r"], dtype=torch.float64)
+        n = int(r.shape[1])
+        self = cls(int(r.shape[0]), nfields, bins, np.asarray(st["mask"], dtype=bool), max(n, int(capacity or 0)),
+                   device=device)
+        if X.dim() != 3 or tuple(X.shape) != (self.nchains, n, self.Jp):
+            raise ValueError("Blackwell-Rao sample bank state: X must be [nchains, n, Jp] of the mask's used columns")
+        self.X[:, :n].copy_(X)
+        self.r[:, :n].copy_(r)
+        self._n = n
+        return self
+
+    def save(self, path):
+        """Write rows [0, n), the tables, the bins, the mask and nfields to an
+        .npz file (numeric arrays only: loads with allow_pickle=False)."""
+        st = self.state()
+        np.savez(path, X=st["X"].numpy(), r=st["r"].numpy(), mask=self.mask, nfields=np.int64(self.nfields),
+                 cols=self.cols.cpu().numpy(), kind=self.kind.cpu().numpy(), coef=self.coef.cpu().numpy(),
+                 **{"bins_" + s: b for s, b in self.bins.items()})
+
+    @classmethod
+    def load(cls, path, device=None):
+        """The bank of a save()d file."""
+        with np.load(path, allow_pickle=False) as f:
+            F = int(f["nfields"])
+            bins = {s: f["bins_" + s] for s in SPECTRA[F]}
+            self = cls.from_state({"X": f["X"], "r": f["r"], "mask": f["mask"]}, F, bins, device=device)
+            if not np.array_equal(f["cols"], self.cols.cpu().numpy()):
+                raise ValueError("Blackwell-Rao sample bank file: its columns do not match its bins and mask")
+        return self
+
+
 def stats_layout(F):
     """Names of the statistic rows (include/gibbs_capi.h GS_NSTAT_*)."""
     return {1: ["ssTT", "dTsT"], 2: ["ssEE", "ssBB", "dEsE", "dBsB"],

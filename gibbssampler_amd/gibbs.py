@@ -51,7 +51,10 @@ and ``keep_scales`` (keep the scale history of the centered conditionals, the
 ``br_likelihood`` ({"theory": {spectrum: [K, nbins]}, "lrange": (lmin, lmax) |
 "mask": ..., "start": ...}: the streaming Blackwell-Rao likelihood of K fixed
 theory spectra, joint over the used bins and the TEB block, the
-``blackwell_rao_likelihood`` property).
+``blackwell_rao_likelihood`` property) and ``br_samples`` (True or {"lrange" |
+"mask": ..., "start": ...}: the Blackwell-Rao sample bank of the used bins'
+scales, kept on the device; the ``blackwell_rao_samples`` property returns it,
+and its ``loglike(theory)`` scores theory spectra named after the run).
 """
 import os
 import time
@@ -160,11 +163,11 @@ class GibbsSampler:
                  chain0=0, reference_quirks=True, noise_pol=None, proposal_variances=None,
                  metropolis_blocks=None, n_iter_metropolis=1, mask_path=None, distributed=False,
                  dist_backend=None, keep_skymap=False, sht_mode="auto", summary=None, keep_history=True,
-                 blackwell_rao=None, keep_scales=False, br_likelihood=None):
+                 blackwell_rao=None, keep_scales=False, br_likelihood=None, br_samples=None):
         self.shard = None
         # streaming posterior summary (samplers.BatchedRunner.run(summary=, keep_history=))
         from .samplers import check_summary
-        check_summary(summary, keep_history or bool(blackwell_rao) or bool(br_likelihood))
+        check_summary(summary, keep_history or bool(blackwell_rao) or bool(br_likelihood) or bool(br_samples))
         self.summary = summary if summary else None
         self.keep_history = bool(keep_history)
         # streaming Blackwell-Rao posteriors and the scale history
@@ -173,6 +176,8 @@ class GibbsSampler:
         self.keep_scales = bool(keep_scales)
         # streaming Blackwell-Rao likelihood of theory spectra (run(br_likelihood=)); checked with the bins
         self.br_likelihood = br_likelihood if br_likelihood else None
+        # Blackwell-Rao sample bank (run(br_samples=)); checked with the bins
+        self.br_samples = br_samples if br_samples else None
         # masked / pixel-TT runs: the Legendre stage of their transforms ("auto":
         # matrix-core tables from 4 chains on small maps, else the recurrence;
         # "recurrence"; "mfma").  Chain b of a batch equals a one-chain run of
@@ -215,9 +220,10 @@ class GibbsSampler:
             self.bins = {s: np.asarray(bins[s]) for s in self.spectra}
         else:
             self.bins = {self.spectra[0]: np.asarray(bins)}
-        from .samplers import check_blackwell_rao, check_br_likelihood
+        from .samplers import check_blackwell_rao, check_br_likelihood, check_br_samples
         check_blackwell_rao(self.blackwell_rao, self.nfields, self.bins)
         check_br_likelihood(self.br_likelihood, self.nfields, self.bins)
+        check_br_samples(self.br_samples, self.nfields, self.bins)
         self.dls_to_cls_array = np.array([2 * np.pi / (l * (l + 1)) if l != 0 else 0 for l in range(lmax + 1)])
         self.noise_pol = noise_pol
         # TT from a pixel map keeps per-pixel noise (the f4 pixel path); the harmonic
@@ -346,8 +352,11 @@ class GibbsSampler:
         resume, self._resume_state = getattr(self, "_resume_state", None), None
         init = dls_init if isinstance(dls_init, dict) or resume is not None else {self.spectra[0]: dls_init}
         kw = {"n_warmup": self.n_warmup, "target_accept": self.target_accept} if self.n_warmup else {}
-        if self.summary is not None or self.blackwell_rao is not None or self.br_likelihood is not None:
+        if self.summary is not None or self.blackwell_rao is not None or self.br_likelihood is not None or \
+                self.br_samples is not None:
             kw.update(summary=self.summary, keep_history=self.keep_history)
+        if self.br_samples is not None:
+            kw.update(br_samples=self.br_samples)
         if self.br_likelihood is not None:
             kw.update(br_likelihood=self.br_likelihood)
         if self.blackwell_rao is not None or self.keep_scales:
@@ -437,6 +446,14 @@ class GibbsSampler:
                 raise NotImplementedError("br_likelihood: masked and TT-pixel runs do not go through the device "
                                           "C_l draw that records the scales; full-sky harmonic (all_sph) runs only")
 
+        if self.br_samples is not None:
+            if self._kind == "noncentered":
+                raise NotImplementedError("br_samples: the non-centered sampler's Metropolis step has no "
+                                          "centered conditional; use CenteredGibbs or ASIS")
+            if self.mask is not None or getattr(self, "tt_pixel", False):
+                raise NotImplementedError("br_samples: masked and TT-pixel runs do not go through the device "
+                                          "C_l draw that records the scales; full-sky harmonic (all_sph) runs only")
+
     @property
     def posterior_summary(self):
         """After a run with summary=: per spectrum a dict of numpy arrays -- mean,
@@ -457,6 +474,16 @@ class GibbsSampler:
         if self._runner is None:
             raise RuntimeError("blackwell_rao_likelihood: nothing has run yet")
         return self._runner.br_likelihood(self.shard.gather if self.shard is not None else None)
+
+    @property
+    def blackwell_rao_samples(self):
+        """After a run with br_samples=: the sample bank (engine.BlackwellRaoSamples)
+        of this rank's chains -- loglike(theory[, gather]) gives {loglike [K],
+        chain_loglike [chains, K], neff [K], n, bad} for theory spectra named
+        after the run, save(path) writes it to an .npz file."""
+        if self._runner is None:
+            raise RuntimeError("blackwell_rao_samples: nothing has run yet")
+        return self._runner.br_samples()
 
     @property
     def blackwell_rao_posterior(self):

@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from . import _capi as C
-from .engine import BlackwellRaoLikelihood, BlackwellRaoState, GibbsPlan, MH_ORDER, SummaryState
+from .engine import BlackwellRaoLikelihood, BlackwellRaoSamples, BlackwellRaoState, GibbsPlan, MH_ORDER, SummaryState
 
 INIT_ITER = 0xFFFFFFFF
 ADAPT_KAPPA = 0.6       # Robbins-Monro step n^-kappa of the warm-up adaptation
@@ -127,6 +127,72 @@ def check_blackwell_rao(br, nfields, bins, dls_init=None, maxbins=None):
     return {"grid": grid, "alpha": alpha, "half_mask": half, "start": None if start is None else int(start)}
 
 
+def _br_theory_array(name, th, spectra, bins, nspec, maxbins):
+    """theory {spectrum: [K, nbins]} or [K, nspec, maxbins] -> fp64 [K, nspec, maxbins]."""
+    if isinstance(th, dict):
+        if set(th) != set(spectra):
+            raise ValueError(f"{name}: theory needs the spectra {list(spectra)}")
+        rows = [np.atleast_2d(np.asarray(th[s], dtype=np.float64)) for s in spectra]
+        K = rows[0].shape[0]
+        theory = np.ones((K, nspec, maxbins))
+        for k, (s, v) in enumerate(zip(spectra, rows)):
+            nb = len(bins[s]) - 1
+            if v.ndim != 2 or v.shape != (K, nb):
+                raise ValueError(f"{name}: theory[{s}] must be [K, nbins] = [{K}, {nb}]")
+            theory[:, k, :nb] = v
+    else:
+        theory = np.array(th, dtype=np.float64)
+        if theory.ndim != 3 or theory.shape[1:] != (nspec, maxbins):
+            raise ValueError(f"{name}: theory must be [K, nspec, maxbins] = [K, {nspec}, {maxbins}]")
+    if theory.shape[0] < 1:
+        raise ValueError(f"{name}: at least one theory spectrum (K >= 1) is needed")
+    return theory
+
+
+def _br_used_mask(name, opts, F, spectra, bins, drawn):
+    """The used bins of the options' lrange or mask (default: every drawn bin)."""
+    from .engine import br_likelihood_mask
+    nspec, maxbins = drawn.shape
+    if "mask" in opts:
+        mk = opts["mask"]
+        if isinstance(mk, dict):
+            mask = np.zeros((nspec, maxbins), dtype=bool)
+            for k, s in enumerate(spectra):
+                v = np.asarray(mk[s], dtype=bool)
+                mask[k, :len(v)] = v
+        else:
+            mask = np.array(mk, dtype=bool)
+            if mask.shape != (nspec, maxbins):
+                raise ValueError(f"{name}: mask must be [nspec, maxbins] = [{nspec}, {maxbins}]")
+        mask &= drawn
+    else:
+        lr = opts.get("lrange")
+        if lr is not None and not (len(lr) == 2 and lr[0] <= lr[1]):
+            raise ValueError(f"{name}: lrange must be (lmin, lmax) with lmin <= lmax")
+        mask = br_likelihood_mask(F, bins, maxbins, lr)
+    if F == 3 and not (np.array_equal(mask[0], mask[1]) and np.array_equal(mask[0], mask[3])):
+        raise ValueError(f"{name}: the TEB block is used as a whole: the mask of TT, EE and TE must agree")
+    if not mask.any():
+        raise ValueError(f"{name}: no bin is used (empty used set)")
+    return mask
+
+
+def _br_theory_values(name, theory, mask, F):
+    """A theory on the used bins: finite; positive but for TE; TEB blocks positive definite."""
+    pos = mask.copy()                       # every used spectrum but TE is a variance
+    if F == 3:
+        pos[3] = False
+    tp = theory[:, pos]
+    if not (np.all(np.isfinite(theory[:, mask])) and np.all(tp > 0)):
+        raise ValueError(f"{name}: theory values must be finite, and positive but for TE, on the used bins")
+    if F == 3:
+        m0 = mask[0]
+        det = theory[:, 0, m0] * theory[:, 1, m0] - theory[:, 3, m0] ** 2
+        if not np.all(det > 0):
+            raise ValueError(f"{name}: a used TEB block of the theory must be positive definite "
+                             "(det = TT EE - TE^2 > 0)")
+
+
 def check_br_likelihood(opts, nfields, bins, maxbins=None):
     """run(br_likelihood=...): None / False (off) or {"theory": {spectrum: [K,
     nbins]} or an array [K, nspec, maxbins], "lrange": (lmin, lmax) or "mask":
@@ -150,60 +216,48 @@ def check_br_likelihood(opts, nfields, bins, maxbins=None):
     spectra = SPECTRA[F]
     drawn = br_likelihood_mask(F, bins, maxbins)
     nspec, maxbins = drawn.shape
-    th = opts["theory"]
-    if isinstance(th, dict):
-        if set(th) != set(spectra):
-            raise ValueError(f"br_likelihood: theory needs the spectra {list(spectra)}")
-        rows = [np.atleast_2d(np.asarray(th[s], dtype=np.float64)) for s in spectra]
-        K = rows[0].shape[0]
-        theory = np.ones((K, nspec, maxbins))
-        for k, (s, v) in enumerate(zip(spectra, rows)):
-            nb = len(bins[s]) - 1
-            if v.ndim != 2 or v.shape != (K, nb):
-                raise ValueError(f"br_likelihood: theory[{s}] must be [K, nbins] = [{K}, {nb}]")
-            theory[:, k, :nb] = v
-    else:
-        theory = np.array(th, dtype=np.float64)
-        if theory.ndim != 3 or theory.shape[1:] != (nspec, maxbins):
-            raise ValueError(f"br_likelihood: theory must be [K, nspec, maxbins] = [K, {nspec}, {maxbins}]")
-    K = theory.shape[0]
-    if K < 1:
-        raise ValueError("br_likelihood: at least one theory spectrum (K >= 1) is needed")
-    if "mask" in opts:
-        mk = opts["mask"]
-        if isinstance(mk, dict):
-            mask = np.zeros((nspec, maxbins), dtype=bool)
-            for k, s in enumerate(spectra):
-                v = np.asarray(mk[s], dtype=bool)
-                mask[k, :len(v)] = v
-        else:
-            mask = np.array(mk, dtype=bool)
-            if mask.shape != (nspec, maxbins):
-                raise ValueError(f"br_likelihood: mask must be [nspec, maxbins] = [{nspec}, {maxbins}]")
-        mask &= drawn
-    else:
-        lr = opts.get("lrange")
-        if lr is not None and not (len(lr) == 2 and lr[0] <= lr[1]):
-            raise ValueError("br_likelihood: lrange must be (lmin, lmax) with lmin <= lmax")
-        mask = br_likelihood_mask(F, bins, maxbins, lr)
-    if F == 3 and not (np.array_equal(mask[0], mask[1]) and np.array_equal(mask[0], mask[3])):
-        raise ValueError("br_likelihood: the TEB block is used as a whole: the mask of TT, EE and TE must agree")
-    if not mask.any():
-        raise ValueError("br_likelihood: no bin is used (empty used set)")
-    pos = mask.copy()                       # every used spectrum but TE is a variance
-    if F == 3:
-        pos[3] = False
-    tp = theory[:, pos]
-    if not (np.all(np.isfinite(theory[:, mask])) and np.all(tp > 0)):
-        raise ValueError("br_likelihood: theory values must be finite, and positive but for TE, on the used bins")
-    if F == 3:
-        m0 = mask[0]
-        det = theory[:, 0, m0] * theory[:, 1, m0] - theory[:, 3, m0] ** 2
-        if not np.all(det > 0):
-            raise ValueError("br_likelihood: a used TEB block of the theory must be positive definite "
-                             "(det = TT EE - TE^2 > 0)")
-    return {"tables": br_likelihood_tables(F, bins, theory, mask), "mask": mask, "K": K,
+    theory = _br_theory_array("br_likelihood", opts["theory"], spectra, bins, nspec, maxbins)
+    mask = _br_used_mask("br_likelihood", opts, F, spectra, bins, drawn)
+    _br_theory_values("br_likelihood", theory, mask, F)
+    return {"tables": br_likelihood_tables(F, bins, theory, mask), "mask": mask, "K": theory.shape[0],
             "start": None if start is None else int(start)}
+
+
+def check_br_samples(opts, nfields, bins, maxbins=None):
+    """run(br_samples=...): None / False (off), True or {"lrange": (lmin, lmax) or
+    "mask": bool [nspec, maxbins] or {spectrum: [nbins]} (default: every drawn
+    bin), "start": as the summary's} -- the bins whose scales the sample bank
+    keeps.  Returns None or {mask, start}."""
+    from .engine import SPECTRA, br_likelihood_mask
+    if opts is None or opts is False:
+        return None
+    if opts is True:
+        opts = {}
+    if not isinstance(opts, dict):
+        raise ValueError("br_samples: True or a dict {[lrange | mask][, start]} is needed")
+    bad = set(opts) - {"lrange", "mask", "start"}
+    if bad:
+        raise ValueError(f"br_samples: unknown options {sorted(bad)}")
+    if "lrange" in opts and "mask" in opts:
+        raise ValueError("br_samples: give either lrange or mask")
+    start = opts.get("start")
+    if start is not None and int(start) < 0:
+        raise ValueError("br_samples: start must be >= 0")
+    F = int(nfields)
+    drawn = br_likelihood_mask(F, bins, maxbins)
+    mask = _br_used_mask("br_samples", opts, F, SPECTRA[F], bins, drawn)
+    return {"mask": mask, "start": None if start is None else int(start)}
+
+
+def br_theory(name, theory, nfields, bins, mask):
+    """A theory {spectrum: [K, nbins]} or [K, nspec, maxbins] as fp64 [K, nspec,
+    maxbins], checked on the used bins `mask` with check_br_likelihood's rules."""
+    from .engine import SPECTRA
+    F = int(nfields)
+    mask = np.asarray(mask, dtype=bool)
+    theory = _br_theory_array(name, theory, SPECTRA[F], bins, mask.shape[0], mask.shape[1])
+    _br_theory_values(name, theory, mask, F)
+    return theory
 
 
 def warmup_of_state(st):
@@ -295,6 +349,10 @@ class BatchedRunner:
         # the device state with its tables and the iteration after which it accumulates
         self._brl = None
         self.brl_start = 0
+        # Blackwell-Rao sample bank (run(br_samples=...)): the kept samples' used
+        # scales on the device and the iteration after which they are kept
+        self._brs = None
+        self.brs_start = 0
 
     def __del__(self):
         # dropped inside another sampler's capture: keep the kept hipGraphs, the
@@ -366,6 +424,8 @@ class BatchedRunner:
             bl = self._brl
             st.update(brl_state=bl.data.cpu().clone(), brl_start=int(self.brl_start),
                       **{"brl_" + k: v for k, v in bl.tables().items()})
+        if self._brs is not None:
+            st.update(brs_start=int(self.brs_start), **{"brs_" + k: v for k, v in self._brs.state().items()})
         if self.rng == "replay":
             name, keys, pos, has_gauss, cached = np.random.get_state()
             st.update(numpy_rng_keys=torch.from_numpy(np.asarray(keys, dtype=np.int64)), numpy_rng_pos=int(pos),
@@ -426,6 +486,13 @@ class BatchedRunner:
             self.brl_start = int(st["brl_start"])
         else:
             self._brl = None
+        # and one without the sample bank's keys
+        if st.get("brs_X") is not None:
+            self._brs = BlackwellRaoSamples.from_state({k: st["brs_" + k] for k in ("X", "r", "mask")}, p.F, p.bins,
+                                                       device=p.device)
+            self.brs_start = int(st["brs_start"])
+        else:
+            self._brs = None
         if self.rng == "replay" and "numpy_rng_keys" in st:
             np.random.set_state(("MT19937", st["numpy_rng_keys"].numpy().astype(np.uint32), st["numpy_rng_pos"],
                                  st["numpy_rng_has_gauss"], st["numpy_rng_cached"]))
@@ -587,6 +654,21 @@ class BatchedRunner:
         res.update(n=out["n"], bad=self._brl.bad().cpu().numpy().copy())
         return res
 
+    # -- Blackwell-Rao sample bank ---------------------------------------------------------
+    def _brs_append(self, scales, capacity, it0, k):
+        """As _br_update, for the sample bank and brs_start."""
+        first = max(it0, self.brs_start) + 1
+        n = it0 + k - first + 1
+        if n > 0:
+            self._brs.append(scales, capacity, first, n)
+
+    def br_samples(self):
+        """The sample bank of the last run(br_samples=...) (engine.BlackwellRaoSamples:
+        loglike(theory, gather), save(path))."""
+        if self._brs is None:
+            raise RuntimeError("br_samples: the last run() kept no sample bank (run(br_samples=...))")
+        return self._brs
+
     def summary_accept_counts(self, gather=None):
         """(counts per spectrum {s: int64 [chains, flags]}, n) of the summarised
         iterations (None for the centered sampler)."""
@@ -696,7 +778,7 @@ class BatchedRunner:
     # -- a whole run --------------------------------------------------------------------
     def run(self, dls_init, n_iter, timings=False, gather=None, graph_chunk=32, resume=None, n_warmup=0,
             target_accept=0.25, summary=None, keep_history=True, blackwell_rao=None, keep_scales=False,
-            br_likelihood=None):
+            br_likelihood=None, br_samples=None):
         """n_iter iterations from dls_init; returns (histories, accepts[, step
         times]).  gather: ShardContext.gather of a torchrun job -- the device
         histories of every rank are all-gathered along the chain axis (global
@@ -737,7 +819,16 @@ class BatchedRunner:
         accumulated from the same scale ring after every chunk replay / eager
         step into 24 B per (chain, model).  Centered and ASIS only; it too
         lifts the need for a summary of keep_history=False, and a resumed
-        state that carries one continues it."""
+        state that carries one continues it.
+        br_samples: None, True or {"lrange": (lmin, lmax) or "mask": ..., "start":
+        ...} -- the Blackwell-Rao sample bank (runner.br_samples()): the scales
+        of the used bins of every iteration after `start` are packed from the
+        same scale ring into a bank on the device after every chunk replay /
+        eager step, 8 (Ju + 1) bytes per chain and iteration over Ju used
+        columns, and bank.loglike(theory) scores theory spectra that need not be
+        known before the run.  Centered and ASIS only; it lifts the need for a
+        summary of keep_history=False, and a resumed state that carries a bank
+        continues it (a state_dict holds the whole bank on the host)."""
         p = self.plan
         n_warmup = check_warmup(self.kind, self.rng, n_warmup, target_accept)
         br_opts = check_blackwell_rao(blackwell_rao, p.F, p.bins, dls_init, p.maxbins)
@@ -748,7 +839,12 @@ class BatchedRunner:
         if brl_opts is not None and self.kind == "noncentered":
             raise NotImplementedError("br_likelihood: the non-centered sampler has no centered conditional draw "
                                       "(use the centered or the ASIS sampler)")
-        sm_opts = check_summary(summary, keep_history or br_opts is not None or brl_opts is not None)
+        brs_opts = check_br_samples(br_samples, p.F, p.bins, p.maxbins)
+        if brs_opts is not None and self.kind == "noncentered":
+            raise NotImplementedError("br_samples: the non-centered sampler has no centered conditional draw "
+                                      "(use the centered or the ASIS sampler)")
+        sm_opts = check_summary(summary, keep_history or br_opts is not None or brl_opts is not None or
+                                brs_opts is not None)
         if p.scale_trace is not None:
             p.cls_scale_trace(None)         # left attached by a run that raised
         self._gather = gather
@@ -786,14 +882,26 @@ class BatchedRunner:
             else:
                 self._brl = BlackwellRaoLikelihood(p.nchains, p.nspec, p.maxbins, brl_opts["tables"], device=p.device)
                 self.brl_start = self.n_warmup if brl_opts["start"] is None else brl_opts["start"]
-        sm, br, brl = self._summary, self._br, self._brl
+        if resume is None or self._brs is None:
+            self._brs = None
+            if brs_opts is not None:
+                self.brs_start = self.n_warmup if brs_opts["start"] is None else brs_opts["start"]
+                self._brs = BlackwellRaoSamples(p.nchains, p.F, p.bins, brs_opts["mask"],
+                                                self.iteration + n_iter - max(self.iteration, self.brs_start),
+                                                device=p.device)
+        sm, br, brl, brs = self._summary, self._br, self._brl, self._brs
+        if brs is not None:
+            if self.kind == "noncentered":
+                raise NotImplementedError("br_samples: the non-centered sampler has no centered conditional draw")
+            # room for this run's iterations after brs_start
+            brs.reserve(brs.n + max(self.iteration + n_iter - max(self.iteration, self.brs_start), 0))
         if br is not None and self.kind == "noncentered":
             raise NotImplementedError("blackwell_rao: the non-centered sampler has no centered conditional draw")
         if brl is not None and self.kind == "noncentered":
             raise NotImplementedError("br_likelihood: the non-centered sampler has no centered conditional draw")
-        if sm is None and br is None and brl is None and not keep_history:
+        if sm is None and br is None and brl is None and brs is None and not keep_history:
             raise ValueError("keep_history=False needs a summary")
-        with_scales = br is not None or brl is not None or keep_scales
+        with_scales = br is not None or brl is not None or brs is not None or keep_scales
         self.h_scales = None
         Hs = p.zeros(n_iter, p.nchains, p.nspec, p.maxbins) if keep_scales else None
         # steps of this run that adapt; warm-up and frozen steps never share a graph
@@ -864,6 +972,8 @@ class BatchedRunner:
                     self._br_update(sc_tr, chunk, self.iteration - k, k)
                 if brl is not None:
                     self._brl_update(sc_tr, chunk, self.iteration - k, k)
+                if brs is not None:
+                    self._brs_append(sc_tr, chunk, self.iteration - k, k)
                 if keep_scales:
                     Hs[done:done + k].copy_(sc_tr[:k] if r0 == 0 else sc_tr[(torch.arange(k) + r0) % chunk])
                 h0, h1 = (0 if done == 0 else off + done), off + done + k
@@ -916,6 +1026,8 @@ class BatchedRunner:
                 self._br_update(sc1, 1, self.iteration - 1, 1)
             if brl is not None:
                 self._brl_update(sc1, 1, self.iteration - 1, 1)
+            if brs is not None:
+                self._brs_append(sc1, 1, self.iteration - 1, 1)
             if keep_scales:
                 Hs[i].copy_(sc1[0])
             if sm is not None:

@@ -436,6 +436,35 @@ int gs_brl_update(void* state, int nchains, int nspec, int maxbins, int K, int J
 int gs_brl_finish(const void* state, int C, int K, const double* cst, double* loglike, double* chain_loglike,
                   double* neff, void* stream);
 
+/* ---- Blackwell-Rao sample bank (gs_brs.hip) -------------------------------------
+ * The samples of a run kept for evaluating theory spectra named afterwards: what
+ * gs_brl_update reads of every scale ring row, compressed to the Ju used columns.
+ * Caller-owned DEVICE buffers, Jp = Ju rounded up to a multiple of 4:
+ *   X [nchains][cap][Jp]  the ring's value at column cols[j] (columns >= Ju: 0)
+ *   r [nchains][cap]      sum_j coef_j log(arg_j), formed as gs_brl_update forms
+ *                         it; NaN for a row that estimator skips
+ * cols, kind, coef: the tables of gs_brl_update (they do not depend on a theory).
+ * gs_brs_append packs iterations first_iteration ... first_iteration + nsteps - 1
+ * of the ring (slot rule of gs_brl_update, nsteps <= capacity) into bank rows
+ * row0 ... row0 + nsteps - 1 of every chain, one launch; a bank row's bits depend
+ * on its ring row alone.
+ * gs_brs_eval scores Y [K][Ju] (engine.br_likelihood_tables) against bank rows
+ * [0, n) on the fp64 matrix cores and writes a state in the layout of gs_brl_bytes
+ * (header with n; m, S, Q [nchains][K]; bad [nchains]) for gs_brl_finish.  work: a
+ * DEVICE buffer of gs_brs_work_bytes(nchains, n, K) bytes (per-slice partials).
+ * The rows of a chain are folded in slices of slice_rows (gs_brs_info) and merged
+ * in a fixed order: for given (n, Ju) the result of (chain, model) is bit-identical
+ * whatever K, the other models and the other chains are; it differs from the
+ * streaming state by the re-ordering of the n weights.  gs_brs.hip documents the
+ * layout and the order of every operation. */
+int gs_brs_info(int* slice_rows /* HOST */, int* model_tile /* HOST */);
+int gs_brs_work_bytes(int nchains, int n, int K, long long* bytes /* HOST */);
+int gs_brs_append(double* X, double* r, int nchains, int cap, int Ju, int nspec, int maxbins, const int* cols,
+                  const int* kind, const double* coef, const double* scales, int capacity, uint32_t first_iteration,
+                  int nsteps, int row0, void* stream);
+int gs_brs_eval(const double* X, const double* r, int nchains, int cap, int n, int Ju, int K, const double* Y,
+                void* work, long long work_bytes, void* state, void* stream);
+
 /* device-side timing of the dominant kernel: with enable = 1 every later CR-sweep
  * launch is bracketed by hipEvents on its stream (also while the stream is
  * captured into a hipGraph: external event-record nodes, timed at each replay);
