@@ -602,7 +602,7 @@ __device__ __forceinline__ void cr_sweep_latency(int L, int nchains, int ntile, 
 #pragma unroll
     for (int k = 0; k < (BM_TAB_DOUBLES + 255) / 256; ++k) {
         const int j = threadIdx.x + 256 * k;
-        tv[k] = j < BM_LOG_DOUBLES ? BM_LOG_TAB[j] : BM_TRIG_TAB[min(j - BM_LOG_DOUBLES, 511)];
+        tv[k] = j < BM_LOG_DOUBLES ? BM_LOG_TAB[j] : BM_TRIG_TAB[min(j - BM_LOG_DOUBLES, BM_TRIG_DOUBLES - 1)];
     }
     // 3. this l's D_l (the latency form always computes the operator in-kernel,
     //    op.mode >= 0; an unbinned l reads bin 0 and drops it)

@@ -126,19 +126,24 @@ __device__ __forceinline__ void bm_sincos2pi(double u, double& sn, double& cs) {
 // doubles that and the Newton step leaves <= 1 ulp (r06: the correctly-rounded
 // second correction cost two fp64 FMAs per normal pair, 1.7 % of the headline
 // step, tools/lib_ab.py; the native streams are checked against the oracle's
-// libm Box-Muller at 1e-10).  Its +-0 / +inf class select becomes a clamp of
-// the seed: for x > 0 here rsq(x) <= 2^26.5 < 2^30 (no change), and for x = +-0
-// the clamped seed carries the signed zero through every step (g0 = x 2^30 =
-// +-0, ..., g2 = +-0 = x, what the select returned).
+// libm Box-Muller at 1e-10).  The Newton step multiplies the residual d0 = x -
+// g1^2 (~2^-43 x) by the first-step half-reciprocal h0 = y0 / 2, not by the
+// refined h1 = h0 + h0 r0: h0 carries the seed's 2^-22 error, so the product is
+// off by ~2^-65 of the root, and h1 with its FMA is gone (the result's error in
+// the seed's error e is 3/2 e^3; <= 1 ulp checked with exact rationals at
+// e = +-2^-22, tests/test_bm_trim_cpu.py).  Its +-0 / +inf class select becomes
+// a clamp of the seed: for x > 0 here rsq(x) <= 2^26.5 < 2^30 (no change), and
+// for x = +-0 the clamped seed (h0 = 2^29, finite) carries the signed zero
+// through every step (g0 = x 2^30 = +-0, g1 = +-0, d0 = +-0, the result +-0 =
+// x, what the select returned).
 __device__ __forceinline__ double bm_sqrt_radius(double x) {
     const double y0 = fmin(fabs(__builtin_amdgcn_rsq(x)), 1073741824.0);
     const double g0 = x * y0;
     const double h0 = y0 * 0.5;
     const double r0 = fma(-h0, g0, 0.5);
     const double g1 = fma(g0, r0, g0);
-    const double h1 = fma(h0, r0, h0);
     const double d0 = fma(-g1, g1, x);
-    return fma(d0, h1, g1);
+    return fma(d0, h0, g1);
 }
 
 __device__ __forceinline__ void box_muller(uint4 w, double& z0, double& z1) {
@@ -241,23 +246,27 @@ __device__ inline void gamma_mt_pair(double alpha0, double alpha1, Key k, uint32
 
 // ---- table-driven fp64 Box-Muller for the CR sweep ------------------------
 // The tables (gs_bm_tables.h, correctly rounded) are staged in LDS (a 16-B
-// aligned array: each cell is one 16-B read) once per workgroup: tab[0..1023] = {c_k, -ln c_k} (512 cells of the frexp mantissa
-// [1/2, 1)), tab[1024..1535] = {sin, cos}(2 pi (k + 1/2) / 256).  Every
+// aligned array: each cell is one 16-B read) once per workgroup: tab[0..1023] = {c_k, 2 ln c_k} (512 cells of the frexp mantissa
+// [1/2, 1)), tab[1024..2047] = {sin, cos}(2 pi (k + 1/2) / 512): 16 KB.  Every
 // operation is fp64; the table cells bound the polynomial arguments (|r| <
-// 1.09e-3 for the log1p, |phi| <= pi / 256 for the trigonometric remainder), so
+// 1.09e-3 for the log1p, |phi| <= pi / 512 for the trigonometric remainder), so
 // low degrees reach ~1 ulp: log1p truncated after r^5 / 5 (relative error <
-// r^5 / 6 < 2.6e-16), sin after phi^5, cos after phi^6 (< 1e-17 absolute).
+// r^5 / 6 < 2.6e-16), sin after phi^5 (< 1e-19 absolute), cos after phi^4
+// (phi^6 / 720 <= 7.3e-17 absolute, a third of the half-ulp of cos phi ~ 1;
+// with 256 cells the phi^6 term was needed: one FMA per pair for 4 KB of LDS,
+// the workgroup's 34 KB still four to a CU).
 // r06: the cells follow the frexp mantissa directly (the r05 table covered
 // [sqrt(1/2), sqrt(2)), which needed a compare, a select, an ldexp and an
 // exponent fix-up per draw, and a float->int index) and are twice as many, and
 // the trig cells are centred, and the log returns -2 ln u (the radius argument,
 // the factor folded into its constants): 11 instructions fewer per normal pair.
 constexpr int BM_LOG_DOUBLES = 2 * BM_LOG_CELLS;
-constexpr int BM_TAB_DOUBLES = BM_LOG_DOUBLES + 512;
+constexpr int BM_TRIG_DOUBLES = 2 * BM_TRIG_CELLS;
+constexpr int BM_TAB_DOUBLES = BM_LOG_DOUBLES + BM_TRIG_DOUBLES;
 
 __device__ __forceinline__ void bm_stage_tables(double* tab) {
     for (int k = threadIdx.x; k < BM_LOG_DOUBLES; k += blockDim.x) tab[k] = BM_LOG_TAB[k];
-    for (int k = threadIdx.x; k < 512; k += blockDim.x) tab[BM_LOG_DOUBLES + k] = BM_TRIG_TAB[k];
+    for (int k = threadIdx.x; k < BM_TRIG_DOUBLES; k += blockDim.x) tab[BM_LOG_DOUBLES + k] = BM_TRIG_TAB[k];
 }
 
 // -2 ln(x 2^-53) for x = K + 1/2 in [1/2, 2^53) (u53's uniform before its exact
@@ -267,6 +276,11 @@ __device__ __forceinline__ void bm_stage_tables(double* tab) {
 // -2 ln x = e (-2 ln 2) + 2 ln c_k - 2 log1p(m c_k - 1), the last term as
 // r (-2 + r (1 + r (-2/3 + r (1/2 - 2/5 r)))).  e <= 0 and ln m < 0 have one
 // sign, and the last cell (m -> 1) has c = 1 exactly, so nothing cancels.
+// -2 ln 2 is its one rounded word: the low word's term, |e| 4.64e-17 <= 2.5e-15
+// absolute, occurs only where the result is at least 1.386 |e|, so it is below
+// 3.4e-17 relative, under a third of an ulp; the whole stays <= 3 ulp (checked
+// with exact rationals over every cell edge and 10^5 uniforms,
+// tests/test_bm_trim_cpu.py).
 __device__ __forceinline__ double bm_m2log_tab(double x, const double* __restrict__ tab) {
     int e;
     const double m = frexp(x, &e);
@@ -281,29 +295,29 @@ __device__ __forceinline__ double bm_m2log_tab(double x, const double* __restric
     q = fma(q, r, 1.0);
     q = fma(q, r, -2.0);
     const double de = (double)e;
-    return fma(de, -1.3862943611198906, fma(de, -4.638093627692599e-17, cv.y + q * r));
+    return fma(de, -1.3862943611198906, cv.y + q * r);
 }
 
 // sin, cos of 2 pi u for u = (K + 0.5) 2^-53, K = (wz >> 5) 2^26 + (ww >> 6):
-// cell k = the top 8 bits (wz >> 24), the remainder angle measured from the
-// cell's centre, phi = (K' + 0.5 - 2^44) 2 pi 2^-53 with K' the low 45 bits
+// cell k = the top 9 bits (wz >> 23), the remainder angle measured from the
+// cell's centre, phi = (K' + 0.5 - 2^43) 2 pi 2^-53 with K' the low 44 bits
 __device__ __forceinline__ void bm_sincos_tab(uint32_t wz, uint32_t ww, const double* __restrict__ tab,
                                               double& sn, double& cs) {
-    const uint32_t k = wz >> 24;
+    static_assert(BM_TRIG_CELLS == 512, "the bit fields below assume 9 index bits");
+    const uint32_t k = wz >> 23;
     // 2^52 + K' as a double from its bits (hi word 0x433 | K' >> 32, lo word the
-    // low 32 bits of K'), less 2^52 + 2^44: K' - 2^44, exact; then one fma
+    // low 32 bits of K'), less 2^52 + 2^43: K' - 2^43, exact; then one fma
     // (y + 1/2) 2 pi 2^-53 (the power-of-two scaling folded into the constant)
-    const uint32_t kh = (wz >> 5) & 0x7FFFFu;                      // K' = kh 2^26 + (ww >> 6)
+    const uint32_t kh = (wz >> 5) & 0x3FFFFu;                      // K' = kh 2^26 + (ww >> 6)
     const uint32_t lo = __builtin_amdgcn_alignbit(kh, ww, 6);      // (kh << 26) | (ww >> 6)
-    const uint32_t hi = ((wz >> 11) & 0x1FFFu) | 0x43300000u;      // 0x433 | kh >> 6
-    const double y = __hiloint2double((int)hi, (int)lo) - 4521191813414912.0;
+    const uint32_t hi = ((wz >> 11) & 0xFFFu) | 0x43300000u;       // 0x433 | kh >> 6
+    const double y = __hiloint2double((int)hi, (int)lo) - 4512395720392704.0;
     constexpr double S = 6.283185307179586 / 9007199254740992.0;
     const double ph = fma(y, S, 0.5 * S);
     const double p2 = ph * ph;
     const double ps = fma(p2, 8.333333333333333e-3, -0.16666666666666666);
     const double sph = fma(ph * p2, ps, ph);
-    double pc = fma(p2, -1.388888888888889e-3, 4.1666666666666664e-2);
-    pc = fma(pc, p2, -0.5);
+    const double pc = fma(p2, 4.1666666666666664e-2, -0.5);
     const double cph = fma(pc, p2, 1.0);
     const double2 tv = reinterpret_cast<const double2*>(tab + BM_LOG_DOUBLES)[k];     // 16-B aligned tab
     const double sk = tv.x, ck = tv.y;

@@ -1,5 +1,5 @@
 """The headline CR sweep's issue ceiling from a MEASURED instruction-class mix
-(VERDICT r05 item 1): the gfx950 ISA of k_cr_sweep<3,0,false,0>'s row loop
+(VERDICT r05 item 1): the gfx950 ISA of k_cr_sweep<3,0,false,0,true>'s row loop
 (hipcc -S of the product source, the loop that holds the three Philox calls),
 each VALU opcode weighted by its measured cycles per wave-instruction at 8
 waves per SIMD (tools/microbench/valu_rate.py -> profiles/r06_valu_rate.json),
@@ -116,7 +116,7 @@ def main():
         priced[cls][1] += n * rates[cls]
         cyc += n * rates[cls]
     wr_plain, wr = wave_rows()
-    out = {"kernel": "k_cr_sweep<3,0,false,0> row loop (gfx950 ISA of the product source)",
+    out = {"kernel": "k_cr_sweep<3,0,false,0,true> row loop, raw moments (gfx950 ISA of the product source)",
            "valu_instructions_per_row": valu, "non_valu_per_row": other,
            "classes": {k: {"count": v[0], "cycles": round(v[1], 1), "cycles_per_instr": rates[k], "measured_w8": raw[k]}
                        for k, v in sorted(priced.items(), key=lambda kv: -kv[1][1])},
