@@ -343,6 +343,243 @@ __global__ __launch_bounds__(BS) void k_brs_combine(const double* __restrict__ p
     }
 }
 
+// ---- likelihood gradient: a second pass over the bank ---------------------------
+// d loglike_k / d Y_kj = -xbar_kj, xbar_kj = sum_ci w_cik x_cij / sum_ci w_cik with
+// w_cik = exp(t_cik - M_k).  k_brs_grad forms the numerators per chain,
+//   num[c][k][j] = sum_i exp(t_cik - mref_k) X[c][i][j],
+// one workgroup (4 waves) per (chain, block of GR = 1024 bank rows, tile of TMOD
+// = 64 models, tile of CT = 128 columns).  The block is walked in passes of PR =
+// 64 rows.  A pass first recomputes t of its 64 rows x 64 models exactly as
+// k_brs_eval does (the same stages of JC = 32 columns over ALL Jp columns, the
+// same MFMA order: the same bits); while a stage of the workgroup's own column
+// tile passes through LDS it is also kept in s_keep [64 rows][CT] (row stride KS =
+// 144 doubles; a row whose r is NaN is kept as zeros, and so are rows >= n).
+// After the last stage a lane holds t of rows 16 wave + (l >> 4) + 4 g and models
+// 16 q + (l & 15) and writes
+//   w = exp((r - dot) - mref_k)      (0 for a NaN r, a row >= n, a model >= K)
+// transposed into s_w [64 models][64 rows] (row stride WS = 66, over the staging
+// buffers).  The second contraction runs over the pass's rows, 4 per MFMA, rows
+// ascending: A = 16 models x 4 rows from s_w (lane l: model l & 15, row l >> 4), B =
+// 4 rows x 16 columns from s_keep (lane l: row l >> 4, column l & 15), D model (l >>
+// 4) + 4 reg, column l & 15.  Wave w owns columns 32 w .. 32 w + 31 of the tile for
+// all 64 models: 8 accumulators (32 doubles) per lane, carried across the passes
+// of the block.  Both reads are conflict-free: the 32 lanes of a ds_read_b64 half
+// fall on 16 models x 2 rows of s_w (dword 132 model + 2 row) and on 2 rows x 16
+// columns of s_keep (dword 288 row + 2 column, 288 = 32 mod 64).
+// The block's tile goes to work [chain][block][K][Jp]; k_brs_grad_combine adds a
+// chain's blocks in block order from 0.0 and writes 0 in the padding columns.  No
+// float atomics: for given (n, Ju, mref_k) the row num[c][k][.] depends on chain
+// c's rows and model k's Y alone.
+// k_brs_grad_finish, one workgroup per model, the chains in chain order, every
+// step one rounded operation:
+//   M = max m_c over S_c > 0,  e_c = S_c exp(m_c - M),  den = sum_c e_c
+//   xbar[k][j] = (sum_c num[c][k][j]) / den,  chain_w[c][k] = e_c / den
+// (NaN where no chain holds a sample; chain_w = 0 for an empty chain among others).
+constexpr int GR = 1024;      // bank rows per workgroup of the gradient pass
+constexpr int CT = 128;       // columns per output tile
+constexpr int KS = CT + 16;   // row stride of the kept X tile (doubles)
+constexpr int WS = PR + 2;    // row stride of the transposed weights (doubles)
+constexpr int NH = CT / (16 * (BS / 64));   // 16-column MFMA tiles per wave
+static_assert(GR % PR == 0 && CT % JC == 0 && NH * 16 * (BS / 64) == CT, "gradient tile shapes");
+static_assert(TMOD * WS <= 2 * PR * LDW, "the weights reuse the staging LDS");
+
+__global__ __launch_bounds__(BS) void k_brs_grad(const double* __restrict__ X, const double* __restrict__ r, int cap,
+                                                 int n, int Jp, int Ju, int K, const double* __restrict__ Y,
+                                                 const double* __restrict__ mref, double* __restrict__ part,
+                                                 int nblk, int nkt, int nct) {
+    __shared__ __attribute__((aligned(16))) double lds[2 * PR * LDW + PR * KS];
+    double* s_x = lds;
+    double* s_y = lds + PR * LDW;
+    double* s_w = lds;                                         // after a pass's last stage
+    double* s_keep = lds + 2 * PR * LDW;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int rl = lane & 15, kq = lane >> 4;
+    int bi = blockIdx.x;
+    const int kt = bi % nkt; bi /= nkt;
+    const int ct = bi % nct; bi /= nct;
+    const int blk = bi % nblk, chain = bi / nblk;
+    const int k0 = kt * TMOD, c0 = ct * CT;
+    const int row_s = blk * GR;
+    const int nrows = n - row_s < GR ? n - row_s : GR;          // > 0: nblk = ceil(n / GR)
+    const int nq = K - k0 >= TMOD ? NQ : (K - k0 + 15) / 16;    // 16-model tiles that hold a model
+    const int cw = c0 + 32 * wave;                              // the wave's first column
+    const int hn = cw >= Jp ? 0 : (Jp - cw > 16 ? NH : 1);      // its 16-column tiles that hold a column
+    const double* Xc = X + (long long)chain * cap * Jp;
+    const double* rc = r + (long long)chain * cap;
+    const int nchunk = (Jp + JC - 1) / JC;
+    const int npass = (nrows + PR - 1) / PR;
+    const int total = npass * nchunk;
+    const int sc = tid & (JC - 1), sr = tid / JC;
+
+    double vx[SE], vy[SE];
+    unsigned vok = 0u;                                         // bit e: row e of the issued stage has a finite r
+    auto issue = [&](int s) {
+        const int pass = s / nchunk, ch = s - pass * nchunk;
+        const int j = ch * JC + sc;
+        if (ch == 0) {
+            vok = 0u;
+#pragma unroll
+            for (int e = 0; e < SE; ++e) {
+                const int lr = pass * PR + sr + (BS / JC) * e;
+                const double rv = lr < nrows ? rc[row_s + lr] : qnan();
+                if (rv == rv) vok |= 1u << e;
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < SE; ++e) {
+            const int lr = pass * PR + sr + (BS / JC) * e;     // row within the block
+            vx[e] = (j < Jp && lr < nrows) ? Xc[(long long)(row_s + lr) * Jp + j] : 0.0;
+            const int km = k0 + sr + (BS / JC) * e;
+            vy[e] = (j < Ju && km < K) ? Y[(long long)km * Ju + j] : 0.0;
+        }
+    };
+
+    double mr[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) mr[q] = (k0 + 16 * q + rl < K) ? mref[k0 + 16 * q + rl] : 0.0;
+    f64x4 acc[NQ];
+    f64x4 nacc[NQ][NH];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q)
+#pragma unroll
+        for (int h = 0; h < NH; ++h) nacc[q][h] = f64x4{0.0, 0.0, 0.0, 0.0};
+    double rr[4];
+
+    issue(0);
+    for (int s = 0; s < total; ++s) {
+        const int pass = s / nchunk, ch = s - pass * nchunk;
+        const bool mine = ch * JC >= c0 && ch * JC < c0 + CT;   // a stage of the workgroup's column tile
+#pragma unroll
+        for (int e = 0; e < SE; ++e) {
+            s_x[(sr + (BS / JC) * e) * LDW + sc] = vx[e];
+            s_y[(sr + (BS / JC) * e) * LDW + sc] = vy[e];
+            if (mine) s_keep[(sr + (BS / JC) * e) * KS + ch * JC - c0 + sc] = ((vok >> e) & 1u) ? vx[e] : 0.0;
+        }
+        __syncthreads();
+        if (s + 1 < total) issue(s + 1);
+        const int wrow = pass * PR + 16 * wave;                 // the wave's first row within the block
+        const bool live = wrow < nrows;
+        if (ch == 0) {
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) acc[q] = f64x4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int lr = wrow + kq + 4 * g;
+                rr[g] = lr < nrows ? rc[row_s + lr] : qnan();
+            }
+        }
+        if (live) {
+            const int left = Jp - ch * JC;
+            const int nks = (left < JC ? left : JC) / 4;
+            const double* ap = s_x + (16 * wave + rl) * LDW + kq;
+            const double* bp = s_y + rl * LDW + kq;
+            for (int ks = 0; ks < nks; ++ks) {
+                const double a = ap[4 * ks];
+                double b[NQ];
+#pragma unroll
+                for (int q = 0; q < NQ; ++q) b[q] = bp[16 * q * LDW + 4 * ks];
+#pragma unroll
+                for (int q = 0; q < NQ; ++q)
+                    if (q < nq) acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b[q], acc[q], 0, 0, 0);
+            }
+        }
+        __syncthreads();                                       // the stage has been read
+        if (ch == nchunk - 1) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const double ri = rr[g];
+#pragma unroll
+                for (int q = 0; q < NQ; ++q) {
+                    double w = 0.0;
+                    if (live && ri == ri && q < nq && k0 + 16 * q + rl < K) w = exp((ri - acc[q][g]) - mr[q]);
+                    s_w[(16 * q + rl) * WS + 16 * wave + kq + 4 * g] = w;
+                }
+            }
+            __syncthreads();
+            const int prow = nrows - pass * PR;                 // rows of this pass (the rest hold w = 0, x = 0)
+            const int nks = ((prow < PR ? prow : PR) + 3) / 4;
+            if (hn > 0) {
+                const double* ap = s_w + rl * WS + kq;
+                const double* bp = s_keep + kq * KS + 32 * wave + rl;
+                for (int ks = 0; ks < nks; ++ks) {
+                    double a[NQ], b[NH];
+#pragma unroll
+                    for (int q = 0; q < NQ; ++q) a[q] = ap[16 * q * WS + 4 * ks];
+#pragma unroll
+                    for (int h = 0; h < NH; ++h) b[h] = bp[4 * ks * KS + 16 * h];
+#pragma unroll
+                    for (int q = 0; q < NQ; ++q)
+#pragma unroll
+                        for (int h = 0; h < NH; ++h)
+                            if (q < nq && h < hn)
+                                nacc[q][h] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[q], b[h], nacc[q][h], 0, 0, 0);
+                }
+            }
+            __syncthreads();                                   // the weights and the kept tile have been read
+        }
+    }
+    double* po = part + ((long long)chain * nblk + blk) * K * Jp;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q)
+#pragma unroll
+        for (int h = 0; h < NH; ++h)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int km = k0 + 16 * q + kq + 4 * g, j = cw + 16 * h + rl;
+                if (q < nq && h < hn && km < K && j < Jp) po[(long long)km * Jp + j] = nacc[q][h][g];
+            }
+}
+
+// one thread per (chain, model, column): the blocks of a chain in block order
+__global__ __launch_bounds__(BS) void k_brs_grad_combine(const double* __restrict__ part, int K, int Jp, int Ju,
+                                                         int nblk, long long total, double* __restrict__ num) {
+    const long long e = (long long)blockIdx.x * BS + threadIdx.x;
+    if (e >= total) return;
+    const long long kj = (long long)K * Jp;
+    const long long chain = e / kj, o = e - chain * kj;
+    double a = 0.0;
+    if ((int)(o % Jp) < Ju)
+        for (int b = 0; b < nblk; ++b) a = add(a, part[(chain * nblk + b) * kj + o]);
+    num[e] = a;
+}
+
+__global__ __launch_bounds__(BS) void k_brs_grad_finish(const double* __restrict__ num, const double* __restrict__ state,
+                                                        int C, int K, int Jp, int Ju, double* __restrict__ xbar,
+                                                        double* __restrict__ chain_w) {
+    const int t = threadIdx.x, k = blockIdx.x;
+    const long long nck = (long long)C * K;
+    const double* fm = state + HDR;
+    const double* fS = fm + nck;
+    bool any = false;
+    double M = 0.0;
+    for (int c = 0; c < C; ++c) {
+        if (fS[(long long)c * K + k] > 0.0) {
+            const double v = fm[(long long)c * K + k];
+            M = any ? fmax(M, v) : v;
+            any = true;
+        }
+    }
+    double den = 0.0;
+    for (int c = 0; c < C; ++c) {
+        const double S = fS[(long long)c * K + k];
+        if (S > 0.0) den = add(den, mul(S, exp(sub(fm[(long long)c * K + k], M))));
+    }
+    for (int j = t; j < Ju; j += BS) {
+        double a = 0.0;
+        for (int c = 0; c < C; ++c) a = add(a, num[((long long)c * K + k) * Jp + j]);
+        xbar[(long long)k * Ju + j] = any ? a / den : qnan();
+    }
+    for (int c = t; c < C; c += BS) {
+        const double S = fS[(long long)c * K + k];
+        double w = 0.0;
+        if (S > 0.0) w = mul(S, exp(sub(fm[(long long)c * K + k], M))) / den;
+        chain_w[(long long)c * K + k] = any ? w : qnan();
+    }
+}
+
+int nblocks(int n) { return (n + GR - 1) / GR; }
+
 int check_bank(const char* what, long long nchains, long long cap, int Ju) {
     if (nchains < 1) return set_error(std::string(what) + ": nchains >= 1 needed");
     if (cap < 1) return set_error(std::string(what) + ": bank capacity cap >= 1 needed");
@@ -425,6 +662,66 @@ int gs_brs_eval(const double* X, const double* r, int nchains, int cap, int n, i
     hipLaunchKernelGGL(k_brs_combine, dim3(kb, (unsigned)nchains), dim3(BS), 0, st, (const double*)work, r, cap, n,
                        nchains, K, nslice, (double*)state);
     GS_LAUNCH_CHECK("k_brs_combine");
+    return 0;
+}
+
+int gs_brs_grad_info(int* block_rows, int* model_tile, int* column_tile) {
+    if (!block_rows || !model_tile || !column_tile) return set_error("gs_brs_grad_info: null argument");
+    *block_rows = GR;
+    *model_tile = TMOD;
+    *column_tile = CT;
+    return 0;
+}
+
+int gs_brs_grad_work_bytes(int nchains, int n, int K, int Ju, long long* bytes) {
+    if (!bytes) return set_error("gs_brs_grad_work_bytes: null argument");
+    if (nchains < 1 || n < 0) return set_error("gs_brs_grad_work_bytes: nchains >= 1 and n >= 0 needed");
+    if (K < 1 || Ju < 1) return set_error("gs_brs_grad_work_bytes: models K >= 1 and used columns Ju >= 1 needed");
+    const long long Jp = (Ju + 3LL) / 4 * 4;
+    *bytes = 8LL * nchains * (long long)(n > 0 ? nblocks(n) : 1) * K * Jp;
+    return 0;
+}
+
+int gs_brs_grad(const double* X, const double* r, int nchains, int cap, int n, int Ju, int K, const double* Y,
+                const double* mref, void* work, long long work_bytes, double* num, void* stream) {
+    if (!X || !r) return set_error("gs_brs_grad: null bank");
+    if (!num) return set_error("gs_brs_grad: null num");
+    if (check_bank("gs_brs_grad", nchains, cap, Ju)) return -1;
+    if (K < 1) return set_error("gs_brs_grad: models K >= 1 needed");
+    if ((long long)nchains * K > (1LL << 28)) return set_error("gs_brs_grad: too many (chain, model) pairs");
+    if (n < 0 || n > cap) return set_error("gs_brs_grad: rows n must lie in [0, cap]");
+    const int Jp = (Ju + 3) / 4 * 4;
+    const long long total = (long long)nchains * K * Jp;
+    if (total > (1LL << 37)) return set_error("gs_brs_grad: num [nchains][K][Jp] too large");
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0) {
+        GS_CHECK(hipMemsetAsync(num, 0, (size_t)(8LL * total), st));
+        return 0;
+    }
+    if (!Y || !mref || !work) return set_error("gs_brs_grad: null Y, mref or workspace");
+    const int nblk = nblocks(n), nkt = (K + TMOD - 1) / TMOD, nct = (Jp + CT - 1) / CT;
+    if (work_bytes < 8LL * nblk * total)
+        return set_error("gs_brs_grad: the workspace is smaller than gs_brs_grad_work_bytes");
+    const long long nb = (long long)nchains * nblk * nkt * nct;
+    if (nb > 0x7fffffffLL) return set_error("gs_brs_grad: too many (chain, block, model tile, column tile) workgroups");
+    hipLaunchKernelGGL(k_brs_grad, dim3((unsigned)nb), dim3(BS), 0, st, X, r, cap, n, Jp, Ju, K, Y, mref,
+                       (double*)work, nblk, nkt, nct);
+    GS_LAUNCH_CHECK("k_brs_grad");
+    hipLaunchKernelGGL(k_brs_grad_combine, dim3((unsigned)((total + BS - 1) / BS)), dim3(BS), 0, st,
+                       (const double*)work, K, Jp, Ju, nblk, total, num);
+    GS_LAUNCH_CHECK("k_brs_grad_combine");
+    return 0;
+}
+
+int gs_brs_grad_finish(const double* num, const void* state, int C, int K, int Ju, double* xbar, double* chain_w,
+                       void* stream) {
+    if (!num || !state || !xbar || !chain_w) return set_error("gs_brs_grad_finish: null argument");
+    if (C < 1 || K < 1 || Ju < 1) return set_error("gs_brs_grad_finish: C, K and Ju >= 1 needed");
+    if ((long long)C * K > (1LL << 28)) return set_error("gs_brs_grad_finish: too many (chain, model) pairs");
+    const int Jp = (Ju + 3) / 4 * 4;
+    hipLaunchKernelGGL(k_brs_grad_finish, dim3((unsigned)K), dim3(BS), 0, (hipStream_t)stream, num,
+                       (const double*)state, C, K, Jp, Ju, xbar, chain_w);
+    GS_LAUNCH_CHECK("k_brs_grad_finish");
     return 0;
 }
 

@@ -650,6 +650,59 @@ def br_likelihood_tables(nfields, bins, theory, mask):
     return {"cols": cols, "kind": kind, "coef": coef, "Y": Y, "cst": np.array([math.fsum(v) for v in cst])}
 
 
+def br_likelihood_grad(nfields, bins, theory, mask, xbar):
+    """The gradient of the Blackwell-Rao log likelihood with respect to the
+    theory spectra, numpy fp64 on the host: [K, nspec, maxbins], exactly 0 on
+    the bins that are not used.  theory and mask as br_likelihood_tables takes
+    them; xbar [K, Ju] is the likelihood-weighted mean of the used scale
+    columns under each theory (columns in the order of the tables' cols), so
+    that d loglike_k / d Y_kj = -xbar_kj and the rest is the chain rule through
+    Y(D) and cst(D) of br_likelihood_tables.  With n_b = l1^2 - l0^2:
+      inverse-Gamma bin: d / dD = xbar / D^2 - (alpha + 1) / D
+      TEB block, Psi = [[xbar_TT, xbar_TE], [xbar_TE, xbar_EE]], D = [[TT, TE],
+        [TE, EE]]:  G = D^-1 Psi D^-1 / 2 - (n_b / 2) D^-1,
+        d / dTT = G_00, d / dEE = G_11, d / dTE = 2 G_01."""
+    F = int(nfields)
+    spectra = SPECTRA[F]
+    theory = np.asarray(theory, dtype=np.float64)
+    mask = np.asarray(mask, dtype=bool)
+    if theory.ndim != 3 or mask.ndim != 2 or theory.shape[1:] != mask.shape or mask.shape[0] != len(spectra):
+        raise ValueError("br_likelihood_grad: theory must be [K, nspec, maxbins] and mask [nspec, maxbins]")
+    K, nspec, maxbins = theory.shape
+    used = mask & br_likelihood_mask(F, bins, maxbins)
+    block = (0, 1, 3) if F == 3 else ()
+    for k in block[1:]:
+        used[k] = used[0]
+    cols = np.flatnonzero(used.reshape(-1))
+    xbar = np.asarray(xbar, dtype=np.float64)
+    if xbar.ndim != 2 or xbar.shape != (K, len(cols)):
+        raise ValueError(f"br_likelihood_grad: xbar must be [K, Ju] = [{K}, {len(cols)}] (the mask's used columns)")
+    pos = {int(c): j for j, c in enumerate(cols)}
+    grad = np.zeros((K, nspec, maxbins))
+    with np.errstate(all="ignore"):
+        for sp, s in enumerate(spectra):
+            if sp in block[1:]:
+                continue
+            e = np.asarray(bins[s], dtype=np.float64)
+            for b in np.flatnonzero(used[sp]):
+                n_b = e[b + 1] ** 2 - e[b] ** 2
+                b = int(b)
+                if sp in block:
+                    tt, ee, te = theory[:, 0, b], theory[:, 1, b], theory[:, 3, b]
+                    ptt, pee, pte = (xbar[:, pos[q * maxbins + b]] for q in (0, 1, 3))
+                    det = tt * ee - te * te
+                    i00, i11, i01 = ee / det, tt / det, -te / det          # D^-1
+                    a00, a01 = i00 * ptt + i01 * pte, i00 * pte + i01 * pee  # D^-1 Psi
+                    a10, a11 = i01 * ptt + i11 * pte, i01 * pte + i11 * pee
+                    grad[:, 0, b] = 0.5 * (a00 * i00 + a01 * i01) - 0.5 * n_b * i00
+                    grad[:, 1, b] = 0.5 * (a10 * i01 + a11 * i11) - 0.5 * n_b * i11
+                    grad[:, 3, b] = (a00 * i01 + a01 * i11) - n_b * i01
+                else:
+                    D = theory[:, sp, b]
+                    grad[:, sp, b] = xbar[:, pos[sp * maxbins + b]] / (D * D) - (0.5 * n_b) / D
+    return grad
+
+
 class BlackwellRaoLikelihood:
     """Streaming Blackwell-Rao likelihood of K theory spectra over the gs_brl_*
     C-ABI (gs_brl.hip documents the state and the order of operations): a flat
@@ -870,6 +923,76 @@ class BlackwellRaoSamples:
                                        C.stream_ptr()), "gs_brl_finish")
         return {"loglike": loglike.cpu().numpy(), "chain_loglike": chain.cpu().numpy(), "neff": neff.cpu().numpy(),
                 "n": self._n, "bad": bad}
+
+    def grad_numerators(self, Y, mref):
+        """num [nchains, K, Jp] (device): num[c, k, j] = sum_i exp(t_cik - mref_k)
+        X[c, i, j] over rows [0, n), a second pass over the bank (gs_brs_grad);
+        Y [K, Ju], mref [K]."""
+        Y = torch.as_tensor(Y, dtype=torch.float64).to(self.device).contiguous()
+        mref = torch.as_tensor(mref, dtype=torch.float64).to(self.device).contiguous()
+        if Y.dim() != 2 or Y.shape[1] != self.Ju or Y.shape[0] < 1 or tuple(mref.shape) != (Y.shape[0],):
+            raise ValueError(f"Blackwell-Rao sample bank: Y must be [K, Ju] = [K, {self.Ju}] and mref [K]")
+        K = int(Y.shape[0])
+        wb = ctypes.c_longlong()
+        C.check(self.lib.gs_brs_grad_work_bytes(self.nchains, self._n, K, self.Ju, ctypes.byref(wb)),
+                "gs_brs_grad_work_bytes")
+        work = torch.empty(wb.value // 8, dtype=torch.float64, device=self.device)
+        num = torch.empty(self.nchains, K, self.Jp, dtype=torch.float64, device=self.device)
+        C.check(self.lib.gs_brs_grad(C.ptr(self.X), C.ptr(self.r), self.nchains, self.capacity, self._n, self.Ju, K,
+                                     C.ptr(Y), C.ptr(mref), C.ptr(work), wb.value, C.ptr(num), C.stream_ptr()),
+                "gs_brs_grad")
+        return num
+
+    def loglike_grad(self, theory, gather=None):
+        """loglike(theory) and its gradient with respect to the theory spectra,
+        numpy: everything loglike returns (the same bits), and
+          grad          {spectrum: [K, nbins]}, d loglike_k / d D^th (0 on the bins
+                        that are not used)
+          mean_scale    [K, nspec, maxbins], the likelihood-weighted mean of the
+                        bank's scales under each theory (NaN off the used set)
+          chain_weight  [C, K], the share of each chain in the estimate
+        (NaN for an empty bank).  A second pass over the bank forms the weighted
+        sums on the matrix cores (gs_brs.hip); engine.br_likelihood_grad is the
+        chain rule.  gather (ShardContext.gather): the state planes, and then the
+        per-chain numerators, are all-gathered along the chain axis."""
+        from .samplers import br_theory
+        th = br_theory("Blackwell-Rao sample bank", theory, self.nfields, self.bins, self.mask)
+        tab = br_likelihood_tables(self.nfields, self.bins, th, self.mask)
+        K = int(tab["Y"].shape[0])
+        Y = torch.from_numpy(np.ascontiguousarray(tab["Y"])).to(self.device)
+        state = self.evaluate(Y)
+        cst = torch.from_numpy(np.ascontiguousarray(tab["cst"])).to(self.device)
+        bad = state[self.HDR + 3 * self.nchains * K:].view(torch.int64).cpu().numpy().copy()
+        nch = self.nchains
+        if gather is not None:
+            body = gather(self.fields(state).contiguous(), dim=1)
+            nch = int(body.shape[1])
+            state = torch.cat([state[:self.HDR], body.reshape(-1)])
+        loglike = torch.zeros(K, dtype=torch.float64, device=self.device)
+        chain = torch.zeros(nch, K, dtype=torch.float64, device=self.device)
+        neff = torch.zeros(K, dtype=torch.float64, device=self.device)
+        C.check(self.lib.gs_brl_finish(C.ptr(state), nch, K, C.ptr(cst), C.ptr(loglike), C.ptr(chain), C.ptr(neff),
+                                       C.stream_ptr()), "gs_brl_finish")
+        # M_k over every (gathered) chain that holds a sample: the weights' reference
+        m, S = (state[self.HDR + p * nch * K:self.HDR + (p + 1) * nch * K].view(nch, K) for p in (0, 1))
+        mref = torch.where(S > 0, m, torch.full_like(m, float("-inf"))).amax(dim=0)
+        mref = torch.where(torch.isinf(mref), torch.zeros_like(mref), mref)
+        num = self.grad_numerators(Y, mref)
+        if gather is not None:
+            num = gather(num, dim=0).contiguous()
+        xbar = torch.zeros(K, self.Ju, dtype=torch.float64, device=self.device)
+        cw = torch.zeros(nch, K, dtype=torch.float64, device=self.device)
+        C.check(self.lib.gs_brs_grad_finish(C.ptr(num), C.ptr(state), nch, K, self.Ju, C.ptr(xbar), C.ptr(cw),
+                                            C.stream_ptr()), "gs_brs_grad_finish")
+        xb = xbar.cpu().numpy()
+        g = br_likelihood_grad(self.nfields, self.bins, th, self.mask, xb)
+        spectra = SPECTRA[self.nfields]
+        mean = np.full((K, self.nspec * self.maxbins), np.nan)
+        mean[:, self.cols.cpu().numpy().astype(np.int64)] = xb
+        return {"loglike": loglike.cpu().numpy(), "chain_loglike": chain.cpu().numpy(), "neff": neff.cpu().numpy(),
+                "n": self._n, "bad": bad,
+                "grad": {s: g[:, k, :len(self.bins[s]) - 1].copy() for k, s in enumerate(spectra)},
+                "mean_scale": mean.reshape(K, self.nspec, self.maxbins), "chain_weight": cw.cpu().numpy()}
 
     # -- checkpoints and files -------------------------------------------------------
     def state(self):

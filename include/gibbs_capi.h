@@ -465,6 +465,37 @@ int gs_brs_append(double* X, double* r, int nchains, int cap, int Ju, int nspec,
 int gs_brs_eval(const double* X, const double* r, int nchains, int cap, int n, int Ju, int K, const double* Y,
                 void* work, long long work_bytes, void* state, void* stream);
 
+/* The gradient of the bank's likelihood with respect to the tables: with w_cik =
+ * exp(t_cik - M_k), d loglike_k / d Y_kj = -xbar_kj, xbar_kj = sum_ci w_cik x_cij /
+ * sum_ci w_cik, the likelihood-weighted mean of the bank's scale columns under
+ * theory k (engine.br_likelihood_grad carries it to d loglike / d D^th).
+ * gs_brs_grad, a second pass over bank rows [0, n) after gs_brs_eval: mref [K]
+ * (DEVICE; the caller's M_k, max_c m_c of the evaluated -- possibly gathered --
+ * state), num [nchains][K][Jp] (DEVICE, output):
+ *   num[c][k][j] = sum_i exp(t_cik - mref_k) x_cij,
+ * t recomputed on the fp64 matrix cores with the bits of gs_brs_eval, the sum over
+ * the rows a second MFMA contraction.  Rows whose r is NaN are never touched; the
+ * padding columns j >= Ju are written as 0; n = 0 zeroes num.  work: a DEVICE
+ * buffer of gs_brs_grad_work_bytes(nchains, n, K, Ju) bytes -- one [K][Jp] tile
+ * per chain and block of block_rows rows, 8 nchains ceil(n / block_rows) K Jp
+ * bytes -- whose blocks are added in block order.  gs_brs_grad_info: block_rows,
+ * the model tile and the column tile (a workgroup recomputes t once per column
+ * tile of its models).  For given (n, Ju, mref_k) the row num[c][k][.] is
+ * bit-identical whatever K, the other models and the other chains are.
+ * gs_brs_grad_finish over the C chains of num [C][K][Jp] and a state in the
+ * layout of gs_brl_bytes (both possibly all-gathered along the chain axis), in
+ * chain order, every step one rounded operation:
+ *   M_k = max m_c over S_c > 0,  den_k = sum_c S_c exp(m_c - M_k)
+ *   xbar [K][Ju] = (sum_c num[c][k][j]) / den_k
+ *   chain_w [C][K] = S_c exp(m_c - M_k) / den_k, the share of a chain in the estimate
+ * NaN where no chain holds a sample. */
+int gs_brs_grad_info(int* block_rows /* HOST */, int* model_tile /* HOST */, int* column_tile /* HOST */);
+int gs_brs_grad_work_bytes(int nchains, int n, int K, int Ju, long long* bytes /* HOST */);
+int gs_brs_grad(const double* X, const double* r, int nchains, int cap, int n, int Ju, int K, const double* Y,
+                const double* mref, void* work, long long work_bytes, double* num, void* stream);
+int gs_brs_grad_finish(const double* num, const void* state, int C, int K, int Ju, double* xbar, double* chain_w,
+                       void* stream);
+
 /* device-side timing of the dominant kernel: with enable = 1 every later CR-sweep
  * launch is bracketed by hipEvents on its stream (also while the stream is
  * captured into a hipGraph: external event-record nodes, timed at each replay);
