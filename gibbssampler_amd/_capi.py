@@ -80,6 +80,7 @@ _SIGS = [
     ("gs_plan_info", ctypes.c_int, [_VP, c_int_p, c_int_p, c_int_p, c_int_p]),
     ("gs_plan_sweep_info", ctypes.c_int, [_VP, c_int_p, c_int_p]),
     ("gs_plan_sweep_pack_info", ctypes.c_int, [_VP, c_int_p, c_int_p]),
+    ("gs_plan_mh_info", ctypes.c_int, [_VP, c_int_p]),
     ("gs_var_expand", ctypes.c_int, [ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
     ("gs_real_to_complex", ctypes.c_int, [ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
     ("gs_complex_to_real", ctypes.c_int, [ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),

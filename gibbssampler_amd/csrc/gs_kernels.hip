@@ -3319,6 +3319,25 @@ static MhPhases mh_phases(int nphase, int lmin, int own, const int (*sp)[2], con
     return h;
 }
 
+// r03: the register / LDS-resident form (k_mh_reg) when the phase l range is at
+// most one l per thread and its arrays fit the LDS (k_mh_fused otherwise);
+// also its LDS bytes and the plan's phase-table entries
+static bool mh_reg_form(const gs_plan* p, size_t* lds_reg_out, int* ntab_out) {
+    int ntab = 0;
+    for (int q = 0; q < p->nphase; ++q) ntab += p->phase_n[q];
+    const size_t lds_reg = (2 * (size_t)(p->L + 1) + (size_t)p->nacc + 3 * (size_t)p->nspec * p->maxbins) *
+                           sizeof(double) + 16 + (size_t)ntab * (sizeof(int4) + sizeof(int2));
+    if (lds_reg_out) *lds_reg_out = lds_reg;
+    if (ntab_out) *ntab_out = ntab;
+    return p->L + 1 - p->mh_lmin <= MH_REG_THREADS && lds_reg <= 150 * 1024;
+}
+
+int gs_plan_mh_info(const gs_plan* p, int* reg_form) {
+    if (check_plan(p)) return -1;
+    if (reg_form) *reg_form = p->has_mh && mh_reg_form(p, nullptr, nullptr) ? 1 : 0;
+    return 0;
+}
+
 // the MH phases proper (proposals already in p->prop / p->logr)
 static int mh_decide(gs_plan* p, const double* stats, double* dl, const double* u_acc, SeedWords sw,
                      uint32_t iteration, int32_t* accept_out, void* stream, const MhEpi* epi = nullptr) {
@@ -3328,18 +3347,12 @@ static int mh_decide(gs_plan* p, const double* stats, double* dl, const double* 
     const bool snap = p->defer.snap_ok;
     p->defer.snap_ok = false;
     int maxnb = 0, ntab = 0;
-    for (int q = 0; q < p->nphase; ++q) {
-        maxnb = std::max(maxnb, p->phase_n[q]);
-        ntab += p->phase_n[q];
-    }
+    for (int q = 0; q < p->nphase; ++q) maxnb = std::max(maxnb, p->phase_n[q]);
     const size_t lds = (2 * (size_t)(p->L + 1) + (size_t)maxnb * p->n_iter_mh + (size_t)p->nspec * p->maxbins) *
                            sizeof(double) + (size_t)p->nspec * (p->L + 1) * sizeof(int);
     const size_t lds_u = u_acc ? (size_t)p->nacc * sizeof(double) : 0;
-    // r03: the register / LDS-resident form when the phase l range is at most
-    // one l per thread and its arrays fit the LDS (k_mh_fused otherwise)
-    const size_t lds_reg = (2 * (size_t)(p->L + 1) + (size_t)p->nacc + 3 * (size_t)p->nspec * p->maxbins) *
-                           sizeof(double) + 16 + (size_t)ntab * (sizeof(int4) + sizeof(int2));
-    const bool reg = p->L + 1 - p->mh_lmin <= MH_REG_THREADS && lds_reg <= 150 * 1024;
+    size_t lds_reg = 0;
+    const bool reg = mh_reg_form(p, &lds_reg, &ntab);
     if (!reg && E.dl_in) {
         // the older MH forms read and write dl in place: copy the input first
         const size_t bytes = (size_t)p->nchains * p->nspec * p->maxbins * sizeof(double);

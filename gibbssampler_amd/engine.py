@@ -93,6 +93,9 @@ class GibbsPlan:
         # packed diagonal workgroups of the no-map throughput sweep, absorbed one-entry groups (per chain)
         C.check(self.lib.gs_plan_sweep_pack_info(h, ctypes.byref(nt), ctypes.byref(rpt)))
         self.sweep_packed, self.sweep_absorbed = nt.value, rpt.value
+        # the NC MH decides in the register form (one multipole per thread) rather than the LDS-phase kernel
+        C.check(self.lib.gs_plan_mh_info(h, ctypes.byref(nt)))
+        self.mh_reg_form = bool(nt.value)
         # host-side replay helpers (data independent)
         ell = np.arange(self.L + 1, dtype=np.float64)
         expo = (2 * ell + 1) / 2

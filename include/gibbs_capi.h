@@ -124,6 +124,9 @@ int gs_plan_sweep_info(const gs_plan* plan, int* ntask, int* rows_per_task);
  * per chain, the workgroups that run the packed form and the one-entry chunk
  * groups they absorb; both 0 where the plan keeps the plain grid alone */
 int gs_plan_sweep_pack_info(const gs_plan* plan, int* npacked, int* nabsorbed);
+/* the form of the NC MH decision launch: reg_form 1 when the plan takes the
+ * register / LDS-resident kernel (one multipole per thread), 0 otherwise */
+int gs_plan_mh_info(const gs_plan* plan, int* reg_form);
 
 /* ---- stand-alone layout / expansion helpers (no plan needed) ---------------- */
 int gs_var_expand(int lmax, int n, const double* dl, double* var, void* stream);

@@ -13,7 +13,8 @@ tools/gen_golden_longchain.py wrote to tests/golden/longchain_nc_teb_L1024_c4.np
   * the per-bin means of the binned D_l over the 100 iterations: 1e-6 relative
     (every spectrum, every chain -- at the reference's blocking TT / EE / TE are
     single whole-range Metropolis blocks and stay at their start; BB moves:
-    ~12.5k accepted blocks per chain);
+    ~12.5k accepted blocks per chain; tests/test_gpu_longchain_small.py runs
+    100-iteration chains in which TT, EE and TE move too);
   * the D_l after iterations 1, 50 and 100: 1e-8 relative;
   * the accept counts per chain and spectrum: exactly.
 """
