@@ -149,6 +149,10 @@ _SIGS = [
     ("gs_brs_grad_work_bytes", ctypes.c_int, [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_longlong)]),
     ("gs_brs_grad", ctypes.c_int, [_VP, _VP] + [ctypes.c_int] * 5 + [_VP, _VP, _VP, ctypes.c_longlong, _VP, _VP]),
     ("gs_brs_grad_finish", ctypes.c_int, [_VP, _VP] + [ctypes.c_int] * 3 + [_VP] * 3),
+    ("gs_brs_hess_info", ctypes.c_int, [c_int_p] * 3),
+    ("gs_brs_hess_work_bytes", ctypes.c_int, [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_longlong)]),
+    ("gs_brs_hess", ctypes.c_int, [_VP, _VP] + [ctypes.c_int] * 5 + [_VP, _VP, _VP, _VP, ctypes.c_longlong, _VP, _VP]),
+    ("gs_brs_hess_finish", ctypes.c_int, [_VP, _VP] + [ctypes.c_int] * 3 + [_VP] * 2),
     ("gs_sht_create", ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(_VP)]),
     ("gs_sht_destroy", ctypes.c_int, [_VP]),
     ("gs_sht_info", ctypes.c_int, [_VP, c_int_p, c_int_p, ctypes.POINTER(ctypes.c_longlong),

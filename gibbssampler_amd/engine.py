@@ -706,6 +706,143 @@ def br_likelihood_grad(nfields, bins, theory, mask, xbar):
     return grad
 
 
+def _br_used(name, nfields, theory, mask, bins):
+    """(theory [K, nspec, maxbins], used bool [nspec, maxbins], cols [Ju], block) as
+    br_likelihood_tables reads them."""
+    F = int(nfields)
+    theory = np.asarray(theory, dtype=np.float64)
+    mask = np.asarray(mask, dtype=bool)
+    if theory.ndim != 3 or mask.ndim != 2 or theory.shape[1:] != mask.shape or mask.shape[0] != len(SPECTRA[F]):
+        raise ValueError(f"{name}: theory must be [K, nspec, maxbins] and mask [nspec, maxbins]")
+    used = mask & br_likelihood_mask(F, bins, theory.shape[2])
+    block = (0, 1, 3) if F == 3 else ()
+    for k in block[1:]:
+        used[k] = used[0]
+    return theory, used, np.flatnonzero(used.reshape(-1)), block
+
+
+def br_likelihood_hess(nfields, bins, theory, mask, xbar, cov):
+    """The Hessian of the Blackwell-Rao log likelihood with respect to the theory
+    spectra, numpy fp64 on the host: H [K, Ju, Ju], parameter j the theory entry
+    at the tables' cols[j] (spectrum * maxbins + bin).  theory, mask and xbar as
+    br_likelihood_grad takes them; cov [K, Ju, Ju] is the likelihood-weighted
+    covariance of the used scale columns under each theory, d^2 loglike_k / dY_ka
+    dY_kb.  H = J^T cov J + L with J = dY / dD and L the Hessian of the single-
+    sample log density with the scale held at xbar, both block diagonal (a bin's Y
+    depends on that bin's D alone).  With n_b = l1^2 - l0^2:
+      inverse-Gamma bin (Y = 1 / D): J = -1 / D^2, L = (n_b / 2) / D^2 - 2 xbar / D^3
+      TEB block, D = [[TT, TE], [TE, EE]], Psi = [[xbar_TT, xbar_TE], [xbar_TE,
+        xbar_EE]], over the basis E_TT, E_EE, E_TE (both off-diagonal entries 1),
+        sum_j x_j Y_j = tr(Psi D^-1) / 2:
+        J[j, U] = -tr(E_j D^-1 U D^-1) / 2
+        L[U, V] = -tr((D^-1 U D^-1 V + D^-1 V D^-1 U) D^-1 Psi) / 2 + (n_b / 2) tr(D^-1 U D^-1 V)
+    The upper triangle is computed and mirrored: H is exactly symmetric."""
+    theory, used, cols, block = _br_used("br_likelihood_hess", nfields, theory, mask, bins)
+    spectra = SPECTRA[int(nfields)]
+    K, nspec, maxbins = theory.shape
+    Ju = len(cols)
+    xbar, cov = np.asarray(xbar, dtype=np.float64), np.asarray(cov, dtype=np.float64)
+    if xbar.shape != (K, Ju) or cov.shape != (K, Ju, Ju):
+        raise ValueError(f"br_likelihood_hess: xbar must be [K, Ju] = [{K}, {Ju}] and cov [K, Ju, Ju] (the mask's used "
+                         "columns)")
+    pos = {int(c): j for j, c in enumerate(cols)}
+    J = np.zeros((K, Ju, Ju))
+    L = np.zeros((K, Ju, Ju))
+    flat = theory.reshape(K, -1)
+    ig, ig_nb, tri, tri_nb = [], [], [], []                     # parameter indices and n_b of the bins, by kind
+    for sp, s in enumerate(spectra):
+        if sp in block[1:]:
+            continue
+        e = np.asarray(bins[s], dtype=np.float64)
+        for b in np.flatnonzero(used[sp]):
+            n_b = e[b + 1] ** 2 - e[b] ** 2
+            if sp in block:
+                tri.append([pos[q * maxbins + int(b)] for q in (0, 1, 3)])
+                tri_nb.append(n_b)
+            else:
+                ig.append(pos[sp * maxbins + int(b)])
+                ig_nb.append(n_b)
+    with np.errstate(all="ignore"):
+        if ig:
+            j = np.array(ig)
+            D = flat[:, cols[j]]
+            J[:, j, j] = -1.0 / (D * D)
+            L[:, j, j] = (0.5 * np.array(ig_nb)) / (D * D) - 2.0 * xbar[:, j] / (D * D * D)
+        if tri:
+            idx = np.array(tri)                                      # [nb, 3]: TT, EE, TE
+            nb2 = 0.5 * np.array(tri_nb)
+            basis = np.array([[[1.0, 0.0], [0.0, 0.0]], [[0.0, 0.0], [0.0, 1.0]], [[0.0, 1.0], [1.0, 0.0]]])
+            tt, ee, te = (flat[:, cols[idx[:, q]]] for q in range(3))    # [K, nb]
+            det = tt * ee - te * te
+            Di = np.stack([np.stack([ee / det, -te / det], axis=-1), np.stack([-te / det, tt / det], axis=-1)], axis=-2)
+            pt, pe, pc = (xbar[:, idx[:, q]] for q in range(3))
+            Psi = np.stack([np.stack([pt, pc], axis=-1), np.stack([pc, pe], axis=-1)], axis=-2)   # [K, nb, 2, 2]
+            WU = np.einsum("knab,ubc->knuac", Di, basis)                 # D^-1 U
+            W = np.einsum("knuab,knbc->knuac", WU, Di)                   # D^-1 U D^-1
+            P = np.einsum("knab,knbc->knac", Di, Psi)                    # D^-1 Psi
+            Jb = -0.5 * np.einsum("uab,knvba->knuv", basis, W)           # [K, nb, j, U]
+            UV = np.einsum("knuab,knvbc->knuvac", WU, WU)                # D^-1 U D^-1 V
+            sym = UV + UV.transpose(0, 1, 3, 2, 4, 5)
+            Lb = -0.5 * np.einsum("knuvab,knba->knuv", sym, P) + nb2[None, :, None, None] * np.einsum("knuvaa->knuv", UV)
+            iu3 = np.triu_indices(3, 1)
+            Lb[:, :, iu3[1], iu3[0]] = Lb[:, :, iu3[0], iu3[1]]
+            J[:, idx[:, :, None], idx[:, None, :]] = Jb
+            L[:, idx[:, :, None], idx[:, None, :]] = Lb
+        # J^T cov J through J's at most 3 entries per column (no dense product): nbr[j] the
+        # parameters of j's block, Jc[k, j, m] = J[k, nbr[j, m], j]
+        ar = np.arange(Ju)
+        nbr = np.repeat(ar[:, None], 3, axis=1)
+        live = np.zeros((Ju, 3), dtype=bool)
+        live[:, 0] = True
+        if tri:
+            for q in range(3):
+                nbr[idx[:, q]] = idx
+                live[idx[:, q]] = True
+        Jc = J[:, nbr, ar[:, None]] * live
+        CJ = sum(cov[:, :, nbr[:, m]] * Jc[:, None, :, m] for m in range(3))
+        H = sum(CJ[:, nbr[:, m], :] * Jc[:, :, m, None] for m in range(3)) + L
+    iu = np.triu_indices(Ju, 1)
+    H[:, iu[1], iu[0]] = H[:, iu[0], iu[1]]
+    return H
+
+
+def br_likelihood_fisher(nfields, bins, mask, hess):
+    """Fisher errors from the Hessian of br_likelihood_hess, numpy fp64 on the host:
+    {fisher [K, Ju, Ju] = -hess, cov [K, Ju, Ju] its inverse, sigma {spectrum: [K,
+    nbins]} the square roots of cov's diagonal (NaN off the used bins)}.  Raises
+    ValueError naming the model when -hess has no Cholesky factor (it is not
+    positive definite, or not finite); no eigenvalue is clipped."""
+    spectra = SPECTRA[int(nfields)]
+    mask = np.asarray(mask, dtype=bool)
+    if mask.ndim != 2 or mask.shape[0] != len(spectra):
+        raise ValueError("br_likelihood_fisher: mask must be bool [nspec, maxbins]")
+    nspec, maxbins = mask.shape
+    _, used, cols, _ = _br_used("br_likelihood_fisher", nfields, np.ones((1, nspec, maxbins)), mask, bins)
+    hess = np.asarray(hess, dtype=np.float64)
+    Ju = len(cols)
+    if hess.ndim != 3 or hess.shape[1:] != (Ju, Ju):
+        raise ValueError(f"br_likelihood_fisher: hess must be [K, Ju, Ju] = [K, {Ju}, {Ju}] (the mask's used columns)")
+    K = hess.shape[0]
+    fisher = -hess
+    cov = np.empty_like(fisher)
+    eye = np.eye(Ju)
+    for k in range(K):
+        try:
+            if not np.all(np.isfinite(fisher[k])):
+                raise np.linalg.LinAlgError("not finite")
+            c = np.linalg.cholesky(fisher[k])
+        except np.linalg.LinAlgError:
+            raise ValueError(f"Blackwell-Rao Fisher matrix: -hess of model {k} is not positive definite (no Cholesky "
+                             "factor): the theory is not at a maximum of the likelihood") from None
+        ci = np.linalg.solve(c, eye)
+        cov[k] = ci.T @ ci
+    sig = np.full((K, nspec * maxbins), np.nan)
+    sig[:, cols] = np.sqrt(np.einsum("kjj->kj", cov))
+    sig = sig.reshape(K, nspec, maxbins)
+    return {"fisher": fisher, "cov": cov,
+            "sigma": {s: sig[:, k, :len(bins[s]) - 1].copy() for k, s in enumerate(spectra)}}
+
+
 class BlackwellRaoLikelihood:
     """Streaming Blackwell-Rao likelihood of K theory spectra over the gs_brl_*
     C-ABI (gs_brl.hip documents the state and the order of operations): a flat
@@ -958,6 +1095,11 @@ class BlackwellRaoSamples:
         sums on the matrix cores (gs_brs.hip); engine.br_likelihood_grad is the
         chain rule.  gather (ShardContext.gather): the state planes, and then the
         per-chain numerators, are all-gathered along the chain axis."""
+        return self._grad_pass(theory, gather)[0]
+
+    def _grad_pass(self, theory, gather):
+        """loglike_grad's dict, and what the Hessian pass goes on from (device: Y,
+        mref, the gathered state and xbar; the checked theory)."""
         from .samplers import br_theory
         th = br_theory("Blackwell-Rao sample bank", theory, self.nfields, self.bins, self.mask)
         tab = br_likelihood_tables(self.nfields, self.bins, th, self.mask)
@@ -992,10 +1134,69 @@ class BlackwellRaoSamples:
         spectra = SPECTRA[self.nfields]
         mean = np.full((K, self.nspec * self.maxbins), np.nan)
         mean[:, self.cols.cpu().numpy().astype(np.int64)] = xb
-        return {"loglike": loglike.cpu().numpy(), "chain_loglike": chain.cpu().numpy(), "neff": neff.cpu().numpy(),
-                "n": self._n, "bad": bad,
-                "grad": {s: g[:, k, :len(self.bins[s]) - 1].copy() for k, s in enumerate(spectra)},
-                "mean_scale": mean.reshape(K, self.nspec, self.maxbins), "chain_weight": cw.cpu().numpy()}
+        out = {"loglike": loglike.cpu().numpy(), "chain_loglike": chain.cpu().numpy(), "neff": neff.cpu().numpy(),
+               "n": self._n, "bad": bad,
+               "grad": {s: g[:, k, :len(self.bins[s]) - 1].copy() for k, s in enumerate(spectra)},
+               "mean_scale": mean.reshape(K, self.nspec, self.maxbins), "chain_weight": cw.cpu().numpy()}
+        return out, {"theory": th, "Y": Y, "mref": mref, "state": state, "nch": nch, "xbar": xbar}
+
+
+    def hess_numerators(self, Y, mref, center):
+        """num2 [nchains, K, Jp, Jp] (device): num2[c, k, a, b] = sum_i exp(t_cik -
+        mref_k) u_cia u_cib over rows [0, n), u_cia = X[c, i, a] - center[k, a], a
+        third pass over the bank (gs_brs_hess); Y [K, Ju], mref [K], center [K, Ju]
+        (the likelihood-weighted mean scales of the complete bank)."""
+        Y = torch.as_tensor(Y, dtype=torch.float64).to(self.device).contiguous()
+        mref = torch.as_tensor(mref, dtype=torch.float64).to(self.device).contiguous()
+        center = torch.as_tensor(center, dtype=torch.float64).to(self.device).contiguous()
+        if Y.dim() != 2 or Y.shape[1] != self.Ju or Y.shape[0] < 1 or tuple(mref.shape) != (Y.shape[0],) or \
+                tuple(center.shape) != tuple(Y.shape):
+            raise ValueError(f"Blackwell-Rao sample bank: Y and center must be [K, Ju] = [K, {self.Ju}] and mref [K]")
+        K = int(Y.shape[0])
+        wb = ctypes.c_longlong()
+        C.check(self.lib.gs_brs_hess_work_bytes(self.nchains, self._n, K, self.Ju, ctypes.byref(wb)),
+                "gs_brs_hess_work_bytes")
+        work = torch.empty(wb.value // 8, dtype=torch.float64, device=self.device)
+        num2 = torch.empty(self.nchains, K, self.Jp, self.Jp, dtype=torch.float64, device=self.device)
+        C.check(self.lib.gs_brs_hess(C.ptr(self.X), C.ptr(self.r), self.nchains, self.capacity, self._n, self.Ju, K,
+                                     C.ptr(Y), C.ptr(mref), C.ptr(center), C.ptr(work), wb.value, C.ptr(num2),
+                                     C.stream_ptr()), "gs_brs_hess")
+        return num2
+
+    def loglike_hess(self, theory, gather=None):
+        """loglike_grad(theory) and the Hessian with respect to the theory spectra,
+        numpy: everything loglike_grad returns (the same bits), and
+          hess       [K, Ju, Ju], d^2 loglike_k / d D^th_a d D^th_b over the used
+                     theory entries
+          scale_cov  [K, Ju, Ju], the likelihood-weighted covariance of the bank's
+                     used scale columns under each theory
+          params     [(spectrum, bin)] of each row and column of the two
+        (NaN for an empty bank).  A third pass over the bank forms the centred
+        second moments on the matrix cores (gs_brh.hip), centred on the gradient
+        pass's mean scales; engine.br_likelihood_hess is the chain rule.  gather
+        (ShardContext.gather): the state planes, the per-chain numerators and then
+        the per-chain second moments are all-gathered along the chain axis."""
+        out, g = self._grad_pass(theory, gather)
+        K = int(g["Y"].shape[0])
+        num2 = self.hess_numerators(g["Y"], g["mref"], g["xbar"])
+        if gather is not None:
+            num2 = gather(num2, dim=0).contiguous()
+        cov = torch.zeros(K, self.Ju, self.Ju, dtype=torch.float64, device=self.device)
+        C.check(self.lib.gs_brs_hess_finish(C.ptr(num2), C.ptr(g["state"]), g["nch"], K, self.Ju, C.ptr(cov),
+                                            C.stream_ptr()), "gs_brs_hess_finish")
+        cv = cov.cpu().numpy()
+        spectra = SPECTRA[self.nfields]
+        out["hess"] = br_likelihood_hess(self.nfields, self.bins, g["theory"], self.mask, g["xbar"].cpu().numpy(), cv)
+        out["scale_cov"] = cv
+        out["params"] = [(spectra[int(c) // self.maxbins], int(c) % self.maxbins) for c in self.cols.cpu().numpy()]
+        return out
+
+    def fisher(self, theory, gather=None):
+        """Fisher errors of the theory spectra at `theory` (a maximum of the
+        likelihood), numpy: {fisher [K, Ju, Ju] = -hess of loglike_hess, cov [K, Ju,
+        Ju] its inverse, sigma {spectrum: [K, nbins]} (NaN off the used bins)}.
+        Raises ValueError naming the model when -hess is not positive definite."""
+        return br_likelihood_fisher(self.nfields, self.bins, self.mask, self.loglike_hess(theory, gather)["hess"])
 
     # -- checkpoints and files -------------------------------------------------------
     def state(self):

@@ -499,6 +499,44 @@ int gs_brs_grad(const double* X, const double* r, int nchains, int cap, int n, i
 int gs_brs_grad_finish(const double* num, const void* state, int C, int K, int Ju, double* xbar, double* chain_w,
                        void* stream);
 
+/* The curvature of the bank's likelihood in the tables (gs_brh.hip):
+ *   d^2 loglike_k / dY_ka dY_kb = Cov_w(x_a, x_b)
+ *     = sum_ci w_cik (x_cia - xbar_ka)(x_cib - xbar_kb) / sum_ci w_cik,
+ * the likelihood-weighted covariance of the bank's scale columns under theory k
+ * (engine.br_likelihood_hess carries it to the Hessian in D^th).
+ * gs_brs_hess, a third pass over bank rows [0, n) after gs_brs_grad_finish: mref
+ * [K] as gs_brs_grad takes it, center [K][Ju] (DEVICE; the caller's xbar of the
+ * complete -- possibly gathered -- bank), num2 [nchains][K][Jp][Jp] (DEVICE,
+ * output):
+ *   num2[c][k][a][b] = sum_i exp(t_cik - mref_k) u_cia u_cib,  u_cia = fl(x_cia - center_ka),
+ * t recomputed with the bits of gs_brs_eval, the sum over the rows an MFMA
+ * contraction of w u against u.  The moments are centred before they are
+ * multiplied: raw second moments minus xbar xbar^T would cancel by the square of
+ * the scales' relative spread.  Each symmetric pair is computed once and written
+ * twice: num2[c][k] is bit-symmetric.  Rows whose r is NaN and rows >= n are never
+ * touched, whatever their X holds; padding rows and columns >= Ju are written as
+ * 0; n = 0 zeroes num2.  work: a DEVICE buffer of gs_brs_hess_work_bytes(nchains,
+ * n, K, Ju) bytes -- one [K][Jp][Jp] tile per chain and block of block_rows rows,
+ * 8 nchains ceil(n / block_rows) K Jp^2 bytes -- whose blocks are added in block
+ * order from 0.0; the call fails when that exceeds 64 GiB (the pass is sized for
+ * a few models: K = 1 ... 16).  gs_brs_hess_info: block_rows, the model tile (a
+ * workgroup recomputes t once for that many models) and the column tile (a
+ * workgroup owns one pair of column tiles a <= b).  For given (n, Ju, mref_k,
+ * center_k) the tile num2[c][k] is bit-identical whatever K, the other models and
+ * the other chains are.
+ * gs_brs_hess_finish over the C chains of num2 [C][K][Jp][Jp] and a state in the
+ * layout of gs_brl_bytes (both possibly all-gathered along the chain axis), in
+ * chain order, every step one rounded operation, den_k as gs_brs_grad_finish
+ * forms it:
+ *   cov [K][Ju][Ju] = (sum_c num2[c][k][a][b]) / den_k
+ * NaN where no chain holds a sample. */
+int gs_brs_hess_info(int* block_rows /* HOST */, int* model_tile /* HOST */, int* column_tile /* HOST */);
+int gs_brs_hess_work_bytes(int nchains, int n, int K, int Ju, long long* bytes /* HOST */);
+int gs_brs_hess(const double* X, const double* r, int nchains, int cap, int n, int Ju, int K, const double* Y,
+                const double* mref, const double* center, void* work, long long work_bytes, double* num2,
+                void* stream);
+int gs_brs_hess_finish(const double* num2, const void* state, int C, int K, int Ju, double* cov, void* stream);
+
 /* device-side timing of the dominant kernel: with enable = 1 every later CR-sweep
  * launch is bracketed by hipEvents on its stream (also while the stream is
  * captured into a hipGraph: external event-record nodes, timed at each replay);
