@@ -153,6 +153,9 @@ _SIGS = [
     ("gs_brs_hess_work_bytes", ctypes.c_int, [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_longlong)]),
     ("gs_brs_hess", ctypes.c_int, [_VP, _VP] + [ctypes.c_int] * 5 + [_VP, _VP, _VP, _VP, ctypes.c_longlong, _VP, _VP]),
     ("gs_brs_hess_finish", ctypes.c_int, [_VP, _VP] + [ctypes.c_int] * 3 + [_VP] * 2),
+    ("gs_brt_tables", ctypes.c_int, [_VP] + [ctypes.c_int] * 4 + [_VP] * 8),
+    ("gs_brt_mref", ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),
+    ("gs_brt_chain", ctypes.c_int, [_VP] * 3 + [ctypes.c_int] * 4 + [_VP] * 8),
     ("gs_sht_create", ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(_VP)]),
     ("gs_sht_destroy", ctypes.c_int, [_VP]),
     ("gs_sht_info", ctypes.c_int, [_VP, c_int_p, c_int_p, ctypes.POINTER(ctypes.c_longlong),

@@ -972,6 +972,7 @@ class BlackwellRaoSamples:
         self.capacity = 0
         self._n = 0
         self.X = self.r = None
+        self._brt = None            # the tables and workspaces of loglike_t / loglike_grad_t, built on first use
         self.reserve(max(int(capacity), 1))
 
     def nbytes(self, capacity):
@@ -1198,6 +1199,191 @@ class BlackwellRaoSamples:
         Raises ValueError naming the model when -hess is not positive definite."""
         return br_likelihood_fisher(self.nfields, self.bins, self.mask, self.loglike_hess(theory, gather)["hess"])
 
+    # -- theories on the device (gs_brt.hip) -----------------------------------------
+    def _brt_tables(self):
+        """The theory-free tables of gs_brt.hip (device; built once): part, cons,
+        inv, and the fiducial [nspec, maxbins] a dict theory's missing spectra take."""
+        if self._brt is not None:
+            return self._brt
+        spectra = SPECTRA[self.nfields]
+        cols = self.cols.cpu().numpy().astype(np.int64)
+        kind = self.kind.cpu().numpy()
+        pos = {int(c): j for j, c in enumerate(cols)}
+        part = np.full((2, self.Ju), -1, dtype=np.int32)
+        cons = np.zeros((2, self.Ju))
+        for j, c in enumerate(cols):
+            sp, b = divmod(int(c), self.maxbins)
+            if kind[j] == 0:
+                continue
+            e = np.asarray(self.bins[spectra[sp]], dtype=np.float64)
+            n_b = e[b + 1] ** 2 - e[b] ** 2
+            cons[0, j] = 0.5 * n_b
+            if kind[j] == 2:
+                nu = n_b - 3.0
+                part[0, j], part[1, j] = pos[self.maxbins + b], pos[3 * self.maxbins + b]
+                lg2 = 0.5 * math.log(math.pi) + math.lgamma(0.5 * nu) + math.lgamma(0.5 * nu - 0.5)
+                cons[1, j] = -nu * math.log(2.0) - lg2
+            else:
+                cons[1, j] = -math.lgamma(0.5 * n_b - 1.0)
+        inv = np.full(self.nspec * self.maxbins, -1, dtype=np.int32)
+        inv[cols] = np.arange(self.Ju, dtype=np.int32)
+        fid = np.ones((self.nspec, self.maxbins))
+        if self.nfields == 3:
+            fid[3] = 0.0
+        dev = self.device
+        self._brt = {"part": torch.from_numpy(part).to(dev).contiguous(), "cons": torch.from_numpy(cons).to(dev).contiguous(),
+                     "inv": torch.from_numpy(inv).to(dev).contiguous(), "fiducial": torch.from_numpy(fid).to(dev),
+                     "ws": {}}
+        return self._brt
+
+    @property
+    def fiducial(self):
+        """Device tensor [nspec, maxbins]: what loglike_t / loglike_grad_t put where a
+        dict theory names no spectrum (and past a spectrum's bins) -- 1 and TE = 0,
+        the values samplers.br_theory pads with, until it is overwritten in place."""
+        return self._brt_tables()["fiducial"]
+
+    def _brt_workspace(self, K, grad):
+        """The buffers of one K (kept on the object; rebuilt when the bank has grown)."""
+        tb = self._brt_tables()
+        ws = tb["ws"].get(K)
+        dev, f64 = self.device, torch.float64
+        if ws is None or ws["n"] != self._n:
+            nb, wb = ctypes.c_longlong(), ctypes.c_longlong()
+            C.check(self.lib.gs_brl_bytes(self.nchains, K, ctypes.byref(nb)), "gs_brl_bytes")
+            C.check(self.lib.gs_brs_work_bytes(self.nchains, self._n, K, ctypes.byref(wb)), "gs_brs_work_bytes")
+            ws = {"n": self._n, "wb": wb.value,
+                  "D": torch.empty(K, self.nspec, self.maxbins, dtype=f64, device=dev),
+                  "Y": torch.zeros(K, self.Ju, dtype=f64, device=dev), "cst": torch.zeros(K, dtype=f64, device=dev),
+                  "bad_model": torch.zeros(K, dtype=torch.int32, device=dev),
+                  "state": torch.zeros(nb.value // 8, dtype=f64, device=dev),
+                  "work": torch.zeros(wb.value // 8, dtype=f64, device=dev),
+                  "loglike": torch.zeros(K, dtype=f64, device=dev),
+                  "chain_loglike": torch.zeros(self.nchains, K, dtype=f64, device=dev),
+                  "neff": torch.zeros(K, dtype=f64, device=dev)}
+            tb["ws"][K] = ws
+        if grad and "grad" not in ws:
+            gb = ctypes.c_longlong()
+            C.check(self.lib.gs_brs_grad_work_bytes(self.nchains, self._n, K, self.Ju, ctypes.byref(gb)),
+                    "gs_brs_grad_work_bytes")
+            ws.update(gb=gb.value, gwork=torch.zeros(gb.value // 8, dtype=f64, device=dev),
+                      mref=torch.zeros(K, dtype=f64, device=dev),
+                      num=torch.zeros(self.nchains, K, self.Jp, dtype=f64, device=dev),
+                      xbar=torch.zeros(K, self.Ju, dtype=f64, device=dev),
+                      chain_weight=torch.zeros(self.nchains, K, dtype=f64, device=dev),
+                      grad=torch.zeros(K, self.nspec, self.maxbins, dtype=f64, device=dev),
+                      mean_scale=torch.zeros(K, self.nspec, self.maxbins, dtype=f64, device=dev))
+        return ws
+
+    def _brt_theory(self, theory):
+        """(K, D [K, nspec, maxbins] contiguous fp64 on the bank's device) of a tensor
+        or a dict of tensors; a dict is packed into the workspace of its K over the
+        fiducial.  Shapes are checked, values are not (gs_brt_tables flags them)."""
+        spectra = SPECTRA[self.nfields]
+        if isinstance(theory, dict):
+            if not theory or set(theory) - set(spectra):
+                raise ValueError(f"Blackwell-Rao sample bank: theory names spectra of {list(spectra)}")
+            vals = {s: v if v.dim() == 2 else v.reshape(1, -1) for s, v in theory.items()}
+            K = int(next(iter(vals.values())).shape[0])
+            for s, v in vals.items():
+                nb = len(self.bins[s]) - 1
+                if not torch.is_tensor(v) or tuple(v.shape) != (K, nb) or v.device != self.device:
+                    raise ValueError(f"Blackwell-Rao sample bank: theory[{s}] must be a tensor [K, nbins] = [{K}, {nb}] "
+                                     "on the bank's device")
+            if K < 1:
+                raise ValueError("Blackwell-Rao sample bank: at least one theory spectrum (K >= 1) is needed")
+            D = self._brt_workspace(K, False)["D"]
+            D.copy_(self.fiducial.unsqueeze(0).expand_as(D))
+            for k, s in enumerate(spectra):
+                if s in vals:
+                    D[:, k, :vals[s].shape[1]].copy_(vals[s])
+            return K, D
+        if not torch.is_tensor(theory) or theory.dim() != 3 or tuple(theory.shape[1:]) != (self.nspec, self.maxbins) or \
+                theory.shape[0] < 1 or theory.device != self.device:
+            raise ValueError("Blackwell-Rao sample bank: theory must be a tensor [K, nspec, maxbins] = "
+                             f"[K, {self.nspec}, {self.maxbins}] on the bank's device (or a dict of tensors)")
+        K = int(theory.shape[0])
+        th = theory.detach()
+        if th.dtype != torch.float64 or not th.is_contiguous():
+            D = self._brt_workspace(K, False)["D"]
+            D.copy_(th)
+            th = D
+        return K, th
+
+    def _brt_pass(self, theory, gather, grad):
+        tb = self._brt_tables()
+        K, D = self._brt_theory(theory)
+        ws = self._brt_workspace(K, grad)
+        st = C.stream_ptr()
+        lib = self.lib
+        C.check(lib.gs_brt_tables(C.ptr(D), K, self.nspec, self.maxbins, self.Ju, C.ptr(self.cols), C.ptr(self.kind),
+                                  C.ptr(tb["part"]), C.ptr(tb["cons"]), C.ptr(ws["Y"]), C.ptr(ws["cst"]),
+                                  C.ptr(ws["bad_model"]), st), "gs_brt_tables")
+        state = ws["state"]
+        C.check(lib.gs_brs_eval(C.ptr(self.X), C.ptr(self.r), self.nchains, self.capacity, self._n, self.Ju, K,
+                                C.ptr(ws["Y"]), C.ptr(ws["work"]), ws["wb"], C.ptr(state), st), "gs_brs_eval")
+        bad = state[self.HDR + 3 * self.nchains * K:].view(torch.int64)
+        nch = self.nchains
+        loglike, chain, neff = ws["loglike"], ws["chain_loglike"], ws["neff"]
+        if gather is not None:
+            body = gather(self.fields(state).contiguous(), dim=1)
+            nch = int(body.shape[1])
+            state = torch.cat([state[:self.HDR], body.reshape(-1)])
+            chain = torch.zeros(nch, K, dtype=torch.float64, device=self.device)
+        C.check(lib.gs_brl_finish(C.ptr(state), nch, K, C.ptr(ws["cst"]), C.ptr(loglike), C.ptr(chain), C.ptr(neff), st),
+                "gs_brl_finish")
+        out = {"loglike": loglike, "chain_loglike": chain, "neff": neff, "n": self._n, "bad": bad,
+               "bad_model": ws["bad_model"]}
+        if not grad:
+            return out
+        C.check(lib.gs_brt_mref(C.ptr(state), nch, K, C.ptr(ws["mref"]), st), "gs_brt_mref")
+        num, cw = ws["num"], ws["chain_weight"]
+        C.check(lib.gs_brs_grad(C.ptr(self.X), C.ptr(self.r), self.nchains, self.capacity, self._n, self.Ju, K,
+                                C.ptr(ws["Y"]), C.ptr(ws["mref"]), C.ptr(ws["gwork"]), ws["gb"], C.ptr(num), st),
+                "gs_brs_grad")
+        if gather is not None:
+            num = gather(num, dim=0).contiguous()
+            cw = torch.zeros(nch, K, dtype=torch.float64, device=self.device)
+        C.check(lib.gs_brs_grad_finish(C.ptr(num), C.ptr(state), nch, K, self.Ju, C.ptr(ws["xbar"]), C.ptr(cw), st),
+                "gs_brs_grad_finish")
+        C.check(lib.gs_brt_chain(C.ptr(D), C.ptr(ws["xbar"]), C.ptr(ws["bad_model"]), K, self.nspec, self.maxbins,
+                                 self.Ju, C.ptr(self.cols), C.ptr(self.kind), C.ptr(tb["part"]), C.ptr(tb["cons"]),
+                                 C.ptr(tb["inv"]), C.ptr(ws["grad"]), C.ptr(ws["mean_scale"]), st), "gs_brt_chain")
+        out.update(grad=ws["grad"], mean_scale=ws["mean_scale"], chain_weight=cw)
+        return out
+
+    def loglike_t(self, theory, gather=None):
+        """loglike() of theories that live on the device, with no host round trip:
+        theory a tensor [K, nspec, maxbins] or {spectrum: tensor [K, nbins]} (packed
+        on the device over `fiducial`) on the bank's device.  Returns loglike [K],
+        chain_loglike [C, K], neff [K] and bad [nchains] as device tensors, n, and
+        bad_model [K] (int32): 1 for a theory loglike() would refuse (a used value
+        not finite or a variance <= 0, a TEB block not positive definite) -- its
+        loglike is NaN, nothing is raised.  The tables are built by gs_brt.hip; the
+        evaluator and the finish are loglike()'s.  Nothing is read back, nothing
+        synchronises and, after the first call with a K, nothing is allocated: with
+        gather=None the call can be captured in a torch.cuda.graph after one warm-up
+        call.  The tensors returned are the bank's workspace of that K: the next call
+        with the same K overwrites them (clone what has to outlive it), and
+        appending rows replaces them."""
+        return self._brt_pass(theory, gather, False)
+
+    def loglike_grad_t(self, theory, gather=None):
+        """loglike_grad() of theories that live on the device: everything loglike_t
+        returns, and grad [K, nspec, maxbins] (d loglike_k / d D^th: exactly 0 off
+        the used bins, NaN for a bad model), mean_scale [K, nspec, maxbins] and
+        chain_weight [C, K], device tensors of the bank's workspace under loglike_t's
+        rules.  The chain rule runs in gs_brt.hip."""
+        return self._brt_pass(theory, gather, True)
+
+    def loglike_torch(self, theory):
+        """loglike [K] of a device tensor theory [K, nspec, maxbins], differentiable:
+        a torch.autograd.Function over loglike_grad_t whose backward is grad_out[:,
+        None, None] * grad of the same pass (no second evaluation).  A theory that
+        does not require a gradient takes loglike_t alone.  The result is a fresh
+        tensor.  Second derivatives are not provided: loglike_hess has them."""
+        return _BankLoglike.apply(theory, self)
+
     # -- checkpoints and files -------------------------------------------------------
     def state(self):
         """Host tensors of rows [0, n) and the mask (what a state_dict carries)."""
@@ -1236,6 +1422,29 @@ class BlackwellRaoSamples:
             if not np.array_equal(f["cols"], self.cols.cpu().numpy()):
                 raise ValueError("Blackwell-Rao sample bank file: its columns do not match its bins and mask")
         return self
+
+
+class _BankLoglike(torch.autograd.Function):
+    """BlackwellRaoSamples.loglike_torch: forward runs loglike_grad_t once and keeps
+    a copy of grad; backward scales its rows.  once_differentiable: a second
+    backward raises."""
+
+    @staticmethod
+    def forward(ctx, theory, bank):
+        if not ctx.needs_input_grad[0]:
+            return bank.loglike_t(theory)["loglike"].clone()
+        out = bank.loglike_grad_t(theory)
+        ctx.save_for_backward(out["grad"].clone())
+        ctx.dtype = theory.dtype
+        return out["loglike"].clone()
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        if grad_out.requires_grad or torch.is_grad_enabled():
+            raise RuntimeError("Blackwell-Rao sample bank: loglike_torch is differentiable once; the second derivatives "
+                               "are loglike_hess(theory)['hess']")
+        grad, = ctx.saved_tensors
+        return (grad_out.to(grad.dtype)[:, None, None] * grad).to(ctx.dtype), None
 
 
 def stats_layout(F):

@@ -537,6 +537,33 @@ int gs_brs_hess(const double* X, const double* r, int nchains, int cap, int n, i
                 void* stream);
 int gs_brs_hess_finish(const double* num2, const void* state, int C, int K, int Ju, double* cov, void* stream);
 
+/* The bank's likelihood of theory spectra that live on the device (gs_brt.hip):
+ * engine.br_likelihood_tables and engine.br_likelihood_grad as kernels, so that
+ * theory -> loglike (-> gradient) runs without a host round trip.  D [K][nspec]
+ * [maxbins] (DEVICE) the theories; cols, kind [Ju] the bank's tables; per used
+ * column j (DEVICE, they do not depend on a theory):
+ *   part [2][Ju]  kind 2 (a block's TT column): the positions of its EE and TE columns
+ *   cons [2][Ju]  n_b / 2, and the theory-free part of the column's cst term
+ *                 (kind 1: -lgamma(alpha); kind 2: -nu log 2 - logGamma_2(nu / 2))
+ *   inv [nspec * maxbins]  the position j of an entry of D, -1 for an unused one
+ * gs_brt_tables writes Y [K][Ju] (the layout gs_brs_eval reads) with the bits of
+ * engine.br_likelihood_tables, cst [K] (the terms added in column order from 0.0
+ * by one thread) and bad [K] (int32): 1 where the host would raise -- a used value
+ * not finite, a variance <= 0, a TEB block with TT EE - TE^2 <= 0; such a model's
+ * Y row and cst are NaN, so its loglike is NaN.
+ * gs_brt_mref: mref [K] = max_c m_c over S_c > 0 of a state in the layout of
+ * gs_brl_bytes (0 where no chain holds a sample), the reference gs_brs_grad takes.
+ * gs_brt_chain carries xbar [K][Ju] of gs_brs_grad_finish to grad [K][nspec]
+ * [maxbins] = d loglike_k / d D with the bits of engine.br_likelihood_grad: exactly
+ * 0.0 on the unused entries, NaN on the used entries of a bad model.  mean (or
+ * NULL): [K][nspec][maxbins], xbar scattered to its entries, NaN elsewhere. */
+int gs_brt_tables(const double* D, int K, int nspec, int maxbins, int Ju, const int* cols, const int* kind,
+                  const int* part, const double* cons, double* Y, double* cst, int* bad, void* stream);
+int gs_brt_mref(const void* state, int C, int K, double* mref, void* stream);
+int gs_brt_chain(const double* D, const double* xbar, const int* bad, int K, int nspec, int maxbins, int Ju,
+                 const int* cols, const int* kind, const int* part, const double* cons, const int* inv, double* grad,
+                 double* mean, void* stream);
+
 /* device-side timing of the dominant kernel: with enable = 1 every later CR-sweep
  * launch is bracketed by hipEvents on its stream (also while the stream is
  * captured into a hipGraph: external event-record nodes, timed at each replay);
