@@ -130,6 +130,12 @@ _SIGS = [
     ("gs_summary_update", ctypes.c_int, [_VP] + [ctypes.c_int] * 5 + [_VP, ctypes.c_int, ctypes.c_uint32, ctypes.c_int,
                                                                        _VP, ctypes.c_longlong, _VP]),
     ("gs_summary_finish", ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [_VP] * 6),
+    ("gs_smap_bytes", ctypes.c_int, [ctypes.c_int, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)]),
+    ("gs_smap_reset", ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_longlong, _VP]),
+    ("gs_smap_update", ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_longlong, _VP, ctypes.c_longlong,
+                                      ctypes.c_longlong, _VP]),
+    ("gs_smap_finish", ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_longlong] + [_VP] * 5),
+    ("gs_smap_power", ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [_VP] * 5),
     ("gs_br_bytes", ctypes.c_int, [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_longlong)]),
     ("gs_br_reset", ctypes.c_int, [_VP] + [ctypes.c_int] * 4 + [_VP]),
     ("gs_br_update", ctypes.c_int, [_VP] + [ctypes.c_int] * 4 + [_VP, _VP, ctypes.c_uint32, _VP, ctypes.c_int,

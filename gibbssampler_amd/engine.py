@@ -474,6 +474,92 @@ class SummaryState:
         return out
 
 
+class SkymapMoments:
+    """Streaming posterior mean and variance of a batch of fp64 series over the
+    gs_smap_* C-ABI (gs_smap.hip documents the state layout and the formulas):
+    a flat fp64 device tensor ``data`` = 8 header doubles (int64 samples per
+    chain first), the Welford mean [nchains, n] and M2 [nchains, n].
+    Plan-independent: n = F (L+1)^2 for a real-layout a_lm, ncomp N_pix for a
+    map.  The sample count is kept on the host as well, so an update reads
+    nothing back; ``data=`` restores a state saved from ``data`` (or rebuilt
+    from ``fields()`` behind its header)."""
+    HDR = 8
+
+    def __init__(self, nchains, n, device=None, data=None):
+        _require_gpu()
+        self.lib = C.load()
+        self.nchains, self.len = int(nchains), int(n)
+        nb = ctypes.c_longlong()
+        C.check(self.lib.gs_smap_bytes(self.nchains, self.len, ctypes.byref(nb)), "gs_smap_bytes")
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+        if data is None:
+            self.data = torch.zeros(nb.value // 8, dtype=torch.float64, device=dev)
+            self._count = 0
+        else:
+            self.data = torch.as_tensor(data, dtype=torch.float64).to(dev).contiguous().clone()
+            if self.data.numel() * 8 != nb.value:
+                raise ValueError("skymap moments: size does not match its dimensions")
+            self._count = int(self.data[:1].view(torch.int64).item())
+
+    def reset(self):
+        C.check(self.lib.gs_smap_reset(C.ptr(self.data), self.nchains, self.len, C.stream_ptr()), "gs_smap_reset")
+        self._count = 0
+
+    def update(self, x, count_after=None):
+        """Add one sample of every chain: x [nchains, ...] (float64, contiguous
+        over the trailing axes, n elements per chain; the chain stride is read
+        from the tensor).  count_after: this sample's number (default: one more
+        than the last update's; pass it when the call is captured in a graph)."""
+        if x.dtype != torch.float64 or not x.is_cuda:
+            raise ValueError("skymap moments: x must be a float64 device tensor")
+        if x.dim() < 1 or x.shape[0] != self.nchains or x.numel() != self.nchains * self.len:
+            raise ValueError(f"skymap moments: x must be [{self.nchains}, ...] with {self.len} elements per chain")
+        if not x[0].is_contiguous():
+            raise ValueError("skymap moments: x must be contiguous over its trailing axes")
+        k = self._count + 1 if count_after is None else int(count_after)
+        C.check(self.lib.gs_smap_update(C.ptr(self.data), self.nchains, self.len, ctypes.c_void_p(x.data_ptr()),
+                                        int(x.stride(0)) if self.nchains > 1 else self.len, k, C.stream_ptr()),
+                "gs_smap_update")
+        self._count = k
+
+    @property
+    def n(self):
+        """Samples per chain (reads the device count: synchronises)."""
+        return int(self.data[:1].view(torch.int64).item())
+
+    def fields(self):
+        """The per-chain fields as a view [2, nchains, n]: mean, M2."""
+        return self.data[self.HDR:].view(2, self.nchains, self.len)
+
+    def finish(self, gather=None):
+        """Device tensors: mean, var, rhat [n], chain_mean [C, n] and n (samples
+        per chain).  gather (ShardContext.gather): the fields are all-gathered
+        along the chain axis first and the finish runs over every rank's chains."""
+        data, nch = self.data, self.nchains
+        if gather is not None:
+            body = gather(self.fields().contiguous(), dim=1)
+            nch = int(body.shape[1])
+            data = torch.cat([self.data[:self.HDR], body.reshape(-1)])
+        z = lambda *shape: torch.zeros(*shape, self.len, dtype=torch.float64, device=self.data.device)
+        mean, var, cm, rhat = z(), z(), z(nch), z()
+        C.check(self.lib.gs_smap_finish(C.ptr(data), nch, self.len, C.ptr(mean), C.ptr(var), C.ptr(cm), C.ptr(rhat),
+                                        C.stream_ptr()), "gs_smap_finish")
+        return dict(mean=mean, var=var, chain_mean=cm, rhat=rhat, n=self.n)
+
+    def power(self, L, F, gather=None, finished=None):
+        """Real-layout a_lm states (n = F (L+1)^2): device tensors power_of_mean
+        and mean_power [F, L+1] (gs_smap_power) of the pooled mean and variance
+        (``finished``: a finish() result to reuse)."""
+        if int(F) * (int(L) + 1) ** 2 != self.len:
+            raise ValueError("skymap moments: power needs n = F (L+1)^2")
+        fin = self.finish(gather) if finished is None else finished
+        pom = torch.zeros(int(F), int(L) + 1, dtype=torch.float64, device=self.data.device)
+        mp = torch.zeros_like(pom)
+        C.check(self.lib.gs_smap_power(int(L), int(F), C.ptr(fin["mean"]), C.ptr(fin["var"]), C.ptr(pom), C.ptr(mp),
+                                       C.stream_ptr()), "gs_smap_power")
+        return dict(power_of_mean=pom, mean_power=mp)
+
+
 def br_shapes(nfields, bins, maxbins=None):
     """The shape table of the centered conditionals (gs_br.hip): (alpha [nspec,
     maxbins], half_mask).  With n_b = l1^2 - l0^2: alpha = n_b / 2 - 1 for the

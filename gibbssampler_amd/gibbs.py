@@ -55,6 +55,9 @@ theory spectra, joint over the used bins and the TEB block, the
 "mask": ..., "start": ...}: the Blackwell-Rao sample bank of the used bins'
 scales, kept on the device; the ``blackwell_rao_samples`` property returns it,
 and its ``loglike(theory)`` scores theory spectra named after the run).
+Masked polarization runs only: ``skymap_summary`` (True or {start, pixels,
+every}: the streaming posterior mean, variance and R-hat of the sky map the CR
+step produces, kept on the device; the ``posterior_skymap`` property).
 """
 import os
 import time
@@ -163,8 +166,13 @@ class GibbsSampler:
                  chain0=0, reference_quirks=True, noise_pol=None, proposal_variances=None,
                  metropolis_blocks=None, n_iter_metropolis=1, mask_path=None, distributed=False,
                  dist_backend=None, keep_skymap=False, sht_mode="auto", summary=None, keep_history=True,
-                 blackwell_rao=None, keep_scales=False, br_likelihood=None, br_samples=None):
+                 blackwell_rao=None, keep_scales=False, br_likelihood=None, br_samples=None, skymap_summary=None):
         self.shard = None
+        # streaming posterior mean / variance of the sky map (masked drivers' run(skymap_summary=))
+        from .samplers import check_skymap_summary
+        check_skymap_summary(skymap_summary)
+        self.skymap_summary = skymap_summary if skymap_summary else None
+        self._masked_runner = None
         # streaming posterior summary (samplers.BatchedRunner.run(summary=, keep_history=))
         from .samplers import check_summary
         check_summary(summary, keep_history or bool(blackwell_rao) or bool(br_likelihood) or bool(br_samples))
@@ -454,6 +462,24 @@ class GibbsSampler:
                 raise NotImplementedError("br_samples: masked and TT-pixel runs do not go through the device "
                                           "C_l draw that records the scales; full-sky harmonic (all_sph) runs only")
 
+    def _check_skymap(self):
+        if self.skymap_summary is not None and (self.mask is None or getattr(self, "tt_pixel", False)):
+            raise NotImplementedError("skymap_summary: full-sky harmonic (all_sph) and TT-pixel runs take their CR "
+                                      "steps inside multi-step launches and captured graphs that have no place "
+                                      "for the per-iteration update; the streaming sky-map posterior covers the "
+                                      "masked polarization drivers only")
+
+    @property
+    def posterior_skymap(self):
+        """After a masked run with skymap_summary=: numpy arrays alm_mean, alm_var,
+        alm_rhat [F, (L+1)^2], chain_alm_mean [chains, F, (L+1)^2], power_of_mean,
+        mean_power [F, L+1], map_mean [F, N_pix] (with pixels: map_var, map_rhat)
+        and n, the samples per chain; over every rank's chains when distributed."""
+        runner = getattr(self, "masked_runner", None) or self._masked_runner
+        if runner is None or getattr(runner, "_skymap", None) is None:
+            raise RuntimeError("posterior_skymap: nothing has run yet with skymap_summary=")
+        return runner.skymap_summary(self.shard.gather if self.shard is not None else None)
+
     @property
     def posterior_summary(self):
         """After a run with summary=: per spectrum a dict of numpy arrays -- mean,
@@ -551,6 +577,7 @@ class CenteredGibbs(GibbsSampler):
         self.cr_ula = ula
         self.tt_pixel = self._tt_pixel_path(all_sph)
         self._check_summary()
+        self._check_skymap()
         if self.tt_pixel:
             from .tt import TTCenteredConstrainedRealization, TTCenteredClsSampler
             m = self._tt_model(False)
@@ -573,7 +600,10 @@ class CenteredGibbs(GibbsSampler):
         if isinstance(s0, dict):
             s0 = np.stack([np.asarray(s0[k]) for k in (("EE", "BB") if F == 2 else ("TT", "EE", "BB"))])
         init = dls_init if isinstance(dls_init, dict) else {self.spectra[0]: dls_init}
-        return runner.run(init, self.n_iter, s0)
+        if self.skymap_summary is None:
+            return runner.run(init, self.n_iter, s0)
+        self._masked_runner = runner
+        return runner.run(init, self.n_iter, s0, skymap_summary=self.skymap_summary)
 
     def run_polarization(self, dls_init):
         """GibbsSampler.run_polarization (GibbsSampler.py:118-180): returns
@@ -607,6 +637,7 @@ class NonCenteredGibbs(GibbsSampler):
         self.tt_pixel = self._tt_pixel_path(all_sph)
         self._set_warmup(n_warmup, target_accept)
         self._check_summary()
+        self._check_skymap()
         if self.tt_pixel:
             from .tt import TTNonCenteredConstrainedRealization, TTNonCenteredClsSampler
             m = self._tt_model(True)
@@ -625,7 +656,8 @@ class NonCenteredGibbs(GibbsSampler):
     def run_polarization(self, dls_init):
         """NonCenteredGibbs.py:529-571: (h_dls, total_accept, h_duration_cr, h_duration_cls)."""
         if self.mask is not None:
-            h, acc = self.masked_runner.run(dls_init, self.n_iter)[:2]
+            kw = {} if self.skymap_summary is None else {"skymap_summary": self.skymap_summary}
+            h, acc = self.masked_runner.run(dls_init, self.n_iter, **kw)[:2]
             return h, acc, np.array([]), np.array([])
         h, acc, t = self._run_common(dls_init)
         return h, acc, np.array([]), np.array([])
@@ -659,6 +691,7 @@ class ASIS(GibbsSampler):
         self.tt_pixel = self._tt_pixel_path(all_sph)
         self._set_warmup(n_warmup, target_accept)
         self._check_summary()
+        self._check_skymap()
         if self.tt_pixel:
             from .tt import TTCenteredConstrainedRealization, TTCenteredClsSampler, TTNonCenteredClsSampler
             m = self._tt_model(True)
@@ -685,7 +718,8 @@ class ASIS(GibbsSampler):
         """ASIS.py:134-226: (h_dls, total_accept, accept_cr|None, h_iteration_duration,
         h_duration_cr, h_duration_cls_sampling, h_duration_cls_nc_sampling)."""
         if self.mask is not None:
-            h, acc, acc_cr, t_it, t_cr, t_cls, t_nc = self.masked_runner.run(dls_init, self.n_iter)
+            kw = {} if self.skymap_summary is None else {"skymap_summary": self.skymap_summary}
+            h, acc, acc_cr, t_it, t_cr, t_cls, t_nc = self.masked_runner.run(dls_init, self.n_iter, **kw)
             return h, acc, (acc_cr if self.rj_step else None), t_it, t_cr, t_cls, t_nc
         h, acc, t = self._run_common(dls_init)
         z = np.zeros(len(t))

@@ -419,6 +419,64 @@ def _unfold_batch(binned_t, idx, valid):
     return torch.where(valid.unsqueeze(0), g, 0.0).contiguous()
 
 
+class SkymapSummary:
+    """The masked drivers' streaming posterior of the sky map (run(skymap_summary=),
+    DESIGN.md 'Posterior sky map'): engine.SkymapMoments of the post-CR a_lm
+    [B, F (L+1)^2] and, with ``pixels``, of the synthesised signal maps
+    [B, ncomp N_pix] (no beam; Q, U for F = 2, T, Q, U for F = 3), updated on the
+    iterations it > start with (it - start - 1) % every == 0."""
+
+    def __init__(self, cr, opt):
+        from .engine import SkymapMoments
+        from .sht import HealpixSHT
+        self.cr, self.start, self.every, self.pixels = cr, opt["start"], opt["every"], opt["pixels"]
+        self.alm = SkymapMoments(cr.B, cr.F * cr.NR, device=torch.device(cr.device))
+        self.sht = HealpixSHT(cr.nside, cr.L)
+        self.pix = SkymapMoments(cr.B, cr.F * cr.Npix, device=torch.device(cr.device)) if self.pixels else None
+        self._maps = None
+
+    def step(self, it, s):
+        """after the CR step of iteration it: s is the map it has just produced"""
+        if it <= self.start or (it - self.start - 1) % self.every:
+            return
+        cr = self.cr
+        a = s.reshape(cr.B, cr.F, cr.NR)
+        self.alm.update(a)
+        if self.pix is not None:
+            self._maps = self.sht.alm2map_batch(a, cr.F, out=self._maps)
+            self.pix.update(self._maps)
+
+    def result(self, gather=None):
+        cr = self.cr
+        F, L = cr.F, cr.L
+        fin = self.alm.finish(gather)
+        pw = self.alm.power(L, F, finished=fin)
+        mean = fin["mean"].reshape(F, cr.NR)
+        host = lambda t, *shape: t.reshape(*shape).cpu().numpy()
+        out = {"alm_mean": host(mean, F, cr.NR), "alm_var": host(fin["var"], F, cr.NR),
+               "alm_rhat": host(fin["rhat"], F, cr.NR), "chain_alm_mean": host(fin["chain_mean"], -1, F, cr.NR),
+               "power_of_mean": host(pw["power_of_mean"], F, L + 1), "mean_power": host(pw["mean_power"], F, L + 1),
+               "map_mean": host(self.sht.alm2map_batch(mean[None], F), F, cr.Npix), "n": fin["n"]}
+        if self.pix is not None:
+            pf = self.pix.finish(gather)
+            out.update(map_var=host(pf["var"], F, cr.Npix), map_rhat=host(pf["rhat"], F, cr.Npix))
+        return out
+
+
+def _skymap_of(runner, cr, skymap_summary):
+    from .samplers import check_skymap_summary
+    opt = check_skymap_summary(skymap_summary)
+    runner._skymap = None if opt is None else SkymapSummary(cr, opt)
+    return runner._skymap
+
+
+def _skymap_result(runner, gather):
+    sm = getattr(runner, "_skymap", None)
+    if sm is None:
+        raise RuntimeError("skymap_summary: no run with skymap_summary= has been made")
+    return sm.result(gather)
+
+
 class MaskedRunner:
     """GibbsSampler.run_polarization (GibbsSampler.py:118-180) for a masked run:
     per iteration the masked CR (MaskedCR, the a12 ladder) and the centered C_l
@@ -444,12 +502,15 @@ class MaskedRunner:
         return _unfold_batch(binned_t, self._idx, self._valid).reshape(self.cr._shape(len(self.spectra),
                                                                                        self.cr.L + 1))
 
-    def run(self, dls_init, n_iter, s_init):
+    def run(self, dls_init, n_iter, s_init, skymap_summary=None):
         """The loop stays on the device: D_l, the accept flags and the histories are
         device tensors until the end (one host transfer per run instead of a sync
         and two copies per iteration); the per-iteration CR / C_l times come from
-        events read after the loop."""
+        events read after the loop.  skymap_summary (True or {start, pixels,
+        every}): stream the posterior mean and variance of the CR maps
+        (``skymap_summary()`` after the run)."""
         cr, plan = self.cr, self.plan
+        smap = _skymap_of(self, cr, skymap_summary)
         if isinstance(dls_init, (list, tuple)):
             binned0 = [{s: np.asarray(d[s], dtype=np.float64) for s in self.spectra} for d in dls_init]
         else:
@@ -480,6 +541,8 @@ class MaskedRunner:
                 cr.step(self.kind, dl, s, iteration=it)
                 acc.append(cr._acc.clone())
             ev[1].record()
+            if smap is not None:
+                smap.step(it, s)
             stats = plan.sweep_stats(self.d0, s.reshape(cr.B, cr.F, cr.NR))
             var = plan.replay_invgamma() if cr.rng == "replay" else None
             binned = plan.cls_draw(stats, var, seed=cr.seed, iteration=it)
@@ -496,6 +559,14 @@ class MaskedRunner:
         h = {sp: (H[:, 0, k, :len(self.bins[sp]) - 1] if one else H[:, :, k, :len(self.bins[sp]) - 1]).copy()
              for k, sp in enumerate(self.spectra)}
         return h, (A[:, 0] if one else A), t_cr, t_cls
+
+    def skymap_summary(self, gather=None):
+        """After run(skymap_summary=): numpy arrays alm_mean, alm_var, alm_rhat
+        [F, (L+1)^2], chain_alm_mean [C, F, (L+1)^2], power_of_mean, mean_power
+        [F, L+1], map_mean [F, N_pix] = alm2map(alm_mean) (with pixels: map_var,
+        map_rhat [F, N_pix]) and n, the samples per chain.  gather
+        (ShardContext.gather): over every rank's chains."""
+        return _skymap_result(self, gather)
 
 
 # ---------------------------------------------------------------------------------------
@@ -664,13 +735,16 @@ class MaskedMHRunner:
     def _pcg(self, dl, it):
         return self.cr.pcg_solve(dl, self.cr.pcg_rhs(dl, iteration=it))
 
-    def run(self, dls_init, n_iter, s_init=None):
+    def run(self, dls_init, n_iter, s_init=None, skymap_summary=None):
         """n_iter iterations from dls_init (binned dict, or a list of B dicts).
         s_init: continue from this map instead of the reference's PCG start map
         (ASIS.py:153-156).  The loop stays on the device (D_l, accept flags and
         histories are device tensors until the end; the stage times come from
-        events read after it)."""
+        events read after it).  skymap_summary (True or {start, pixels, every}):
+        stream the posterior mean and variance of the maps the CR step produces,
+        before non-centring and re-centring (``skymap_summary()`` after the run)."""
         cr, mh, plan = self.cr, self.mh, self.plan
+        smap = _skymap_of(self, cr, skymap_summary)
         B = cr.B
         if isinstance(dls_init, (list, tuple)):
             init = [{s: np.asarray(d[s], dtype=np.float64) for s in mh.spectra} for d in dls_init]
@@ -692,6 +766,8 @@ class MaskedMHRunner:
             ev[0].record()
             if self.kind == "noncentered":
                 s = self._pcg(dl, it)
+                if smap is not None:
+                    smap.step(it, s)
                 s_nc = mh.noncentre(dl, s)
                 ev[1].record()
                 ev[2].record()
@@ -704,6 +780,8 @@ class MaskedMHRunner:
                     cr.step(self.cr_kind, dl, s, iteration=it)
                     acc_cr.append(cr._acc.clone())
                 ev[1].record()
+                if smap is not None:
+                    smap.step(it, s)
                 stats = plan.sweep_stats(self.d0[None], s.reshape(B, cr.F, cr.NR))
                 var = plan.replay_invgamma() if cr.rng == "replay" else None
                 tmp = plan.cls_draw(stats, var, seed=cr.seed, iteration=it)
@@ -741,3 +819,7 @@ class MaskedMHRunner:
             a_cr = a_cr[:, 0]
         out = (h, {sp: np.array(v) for sp, v in acc.items()})
         return out + (a_cr, t_it, t_cr, t_cls, t_nc)
+
+    def skymap_summary(self, gather=None):
+        """After run(skymap_summary=): as MaskedRunner.skymap_summary."""
+        return _skymap_result(self, gather)

@@ -67,6 +67,26 @@ def check_summary(summary, keep_history=True):
     return max_lag, None if start is None else int(start)
 
 
+def check_skymap_summary(opt):
+    """run(skymap_summary=...) of the masked drivers: None / False (off), True,
+    or {start: None, pixels: False, every: 1}; returns None or the dict
+    {start, pixels, every} (start None -> 0: every iteration is summarised)."""
+    if opt is None or opt is False:
+        return None
+    opts = {} if opt is True else dict(opt)
+    bad = set(opts) - {"start", "pixels", "every"}
+    if bad:
+        raise ValueError(f"skymap_summary: unknown options {sorted(bad)}")
+    start = opts.get("start")
+    start = 0 if start is None else int(start)
+    if start < 0:
+        raise ValueError("skymap_summary: start must be >= 0")
+    every = int(opts.get("every", 1))
+    if every < 1:
+        raise ValueError("skymap_summary: every must be >= 1")
+    return {"start": start, "pixels": bool(opts.get("pixels", False)), "every": every}
+
+
 def check_blackwell_rao(br, nfields, bins, dls_init=None, maxbins=None):
     """run(blackwell_rao=...): None / False (off), {"grid": array [nspec, maxbins,
     G]} or {"points": G, "span": (lo, hi)} (a geometric grid dls_init[bin] * lo

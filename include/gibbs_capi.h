@@ -360,6 +360,42 @@ int gs_summary_update(void* state, int nchains, int nspec, int maxbins, int nacc
 int gs_summary_finish(const void* state, int C, int nspec, int maxbins, int max_lag, double* pooled,
                       double* chain_mean, double* chain_var, double* acf, double* gamma, void* stream);
 
+/* ---- streaming posterior mean and variance of the sky map (gs_smap.hip) ---------
+ * Plan-independent moments of a batch of fp64 series: C chains of length n
+ * (n = F (L+1)^2 for a real-layout a_lm, ncomp N_pix for a map).  The state is
+ * a caller-owned DEVICE buffer of gs_smap_bytes bytes (8-byte aligned; 16-byte
+ * aligned for the widest accesses): 8 header doubles (int64 samples per chain
+ * first), then the Welford mean [C][n] and M2 [C][n].
+ * gs_smap_reset zeroes the state.
+ * gs_smap_update adds one sample of every chain, chain c at x + c *
+ * x_chain_stride (elements; n contiguous doubles), as sample number
+ * count_after (1 for the first after a reset): d = x - mean; mean += d / k;
+ * M2 += d (x - mean).  The count comes from the host, so nothing is read back
+ * and the call is capturable; it allocates nothing.  One thread owns an
+ * element and there are no atomics: the state's bits depend neither on the
+ * launch geometry nor on C (chain b of a C-chain state = a one-chain state fed
+ * chain b's data).  Successive updates of one state must be ordered on one
+ * stream.
+ * gs_smap_finish merges the C chains of a state in chain order (Chan's pairwise
+ * update; C need not be the updating context's chain count: per-chain fields
+ * all-gathered along the chain axis are merged over every rank's chains) with
+ * the header's count k per chain.  Outputs, DEVICE fp64: mean [n], var [n] =
+ * M2_total / (C k - 1) (NaN when C k < 2), chain_mean [C][n], rhat [n]
+ * (Gelman-Rubin as gs_summary_finish; NaN for C = 1, k < 2 or W == 0).
+ * gs_smap_power, for a real-layout a_lm state's pooled mean and var [F][(L+1)^2]:
+ * per field and l, power_of_mean [F][L+1] = sum_m mean^2 / (2l+1), the spectrum
+ * of the posterior mean map, and mean_power [F][L+1] = power_of_mean +
+ * sum_m var / (2l+1), the posterior mean of the map's spectrum (auto spectra
+ * only), summed in the fixed order m = 0, 1, .. l. */
+int gs_smap_bytes(int C, long long n, long long* bytes /* HOST */);
+int gs_smap_reset(void* state, int C, long long n, void* stream);
+int gs_smap_update(void* state, int C, long long n, const double* x, long long x_chain_stride, long long count_after,
+                   void* stream);
+int gs_smap_finish(const void* state, int C, long long n, double* mean, double* var, double* chain_mean, double* rhat,
+                   void* stream);
+int gs_smap_power(int lmax, int nfields, const double* mean, const double* var, double* power_of_mean,
+                  double* mean_power, void* stream);
+
 /* ---- streaming Blackwell-Rao marginal posteriors of the D_l (gs_br.hip) -------
  * The centered C_l draw samples D_b | s from an inverse-Gamma(alpha_b, beta_b)
  * (PolarizedCenteredClsSampler.sample, CenteredGibbs.py:54-93); the Blackwell-Rao
