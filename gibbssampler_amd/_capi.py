@@ -136,6 +136,13 @@ _SIGS = [
                                       ctypes.c_longlong, _VP]),
     ("gs_smap_finish", ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_longlong] + [_VP] * 5),
     ("gs_smap_power", ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [_VP] * 5),
+    ("gs_wf_bytes", ctypes.c_int, [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_longlong)]),
+    ("gs_wf_reset", ctypes.c_int, [_VP] + [ctypes.c_int] * 3 + [_VP]),
+    ("gs_wf_moments", ctypes.c_int, [ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
+    ("gs_wf_update", ctypes.c_int, [_VP] + [ctypes.c_int] * 4 + [_VP, _VP] + [ctypes.c_double] * 3 + [_VP, _VP,
+                                    ctypes.c_int, ctypes.c_uint32, ctypes.c_int, ctypes.c_longlong, _VP]),
+    ("gs_wf_finish", ctypes.c_int, [_VP] + [ctypes.c_int] * 3 + [_VP] * 6),
+    ("gs_wf_power", ctypes.c_int, [_VP] + [ctypes.c_int] * 3 + [_VP] * 5),
     ("gs_br_bytes", ctypes.c_int, [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_longlong)]),
     ("gs_br_reset", ctypes.c_int, [_VP] + [ctypes.c_int] * 4 + [_VP]),
     ("gs_br_update", ctypes.c_int, [_VP] + [ctypes.c_int] * 4 + [_VP, _VP, ctypes.c_uint32, _VP, ctypes.c_int,

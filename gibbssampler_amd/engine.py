@@ -560,6 +560,143 @@ class SkymapMoments:
         return dict(power_of_mean=pom, mean_power=mp)
 
 
+class WienerPosterior:
+    """Rao-Blackwellised posterior sky map of a full-sky run over the gs_wf_*
+    C-ABI (gs_wf.hip documents the state layout and the formulas): from the
+    D_l trace ring alone, through the closed-form centered operator M_l(D_l),
+    Sigma_l(D_l) of the plan's tables -- the beam bl [L+1], the bins {spectrum:
+    edges} and the noise weights N_pix / (4 pi noise_var_f).  ``data`` is a flat
+    fp64 device tensor: 8 header doubles (int64 samples per chain first), then
+    the planes [NFLD, nchains, L+1].  The sample count is kept on the host as
+    well, so an update reads nothing back; ``data=`` restores a saved state."""
+    HDR = 8
+
+    def __init__(self, nfields, lmax, nchains, bl, bins, noise_weights, maxbins=None, device=None, data=None):
+        _require_gpu()
+        self.lib = C.load()
+        self.F, self.L, self.nchains = int(nfields), int(lmax), int(nchains)
+        self.spectra = SPECTRA[self.F]
+        self.nspec, self.nop = len(self.spectra), 5 if self.F == 3 else self.F
+        self.nfld = 20 if self.F == 3 else 4 * self.F
+        self.NR = (self.L + 1) ** 2
+        nb = ctypes.c_longlong()
+        C.check(self.lib.gs_wf_bytes(self.F, self.nchains, self.L, ctypes.byref(nb)), "gs_wf_bytes")
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+        bl = np.ascontiguousarray(bl, dtype=np.float64)
+        if bl.shape != (self.L + 1,):
+            raise ValueError("wiener posterior: bl must have lmax + 1 entries")
+        kap = [float(v) for v in np.atleast_1d(noise_weights)]
+        if len(kap) != self.F or not all(v > 0 for v in kap):
+            raise ValueError("wiener posterior: one positive noise weight per field is needed")
+        self.kappa = kap + [0.0] * (3 - self.F)
+        e2b = np.full((self.nspec, self.L + 1), -1, dtype=np.int32)
+        nbins = []
+        for k, s in enumerate(self.spectra):
+            e = np.asarray(bins[s], dtype=np.int64)
+            if len(e) < 2 or e[0] < 0 or np.any(np.diff(e) < 0) or e[-1] > self.L + 1:
+                raise ValueError(f"wiener posterior: invalid bin edges for {s}")
+            nbins.append(len(e) - 1)
+            for i in range(len(e) - 1):
+                e2b[k, e[i]:e[i + 1]] = i
+        self.maxbins = max(nbins) if maxbins is None else int(maxbins)
+        if self.maxbins < max(nbins):
+            raise ValueError("wiener posterior: maxbins is smaller than a spectrum's bin count")
+        self.bl = torch.from_numpy(bl).to(dev)
+        self.ell2bin = torch.from_numpy(e2b).to(dev)
+        self.moments = None
+        if data is None:
+            self.data = torch.zeros(nb.value // 8, dtype=torch.float64, device=dev)
+            self._count = 0
+        else:
+            self.data = torch.as_tensor(data, dtype=torch.float64).to(dev).contiguous().clone()
+            if self.data.numel() * 8 != nb.value:
+                raise ValueError("wiener posterior: size does not match its dimensions")
+            self._count = int(self.data[:1].view(torch.int64).item())
+
+    @classmethod
+    def from_plan(cls, plan, nchains=None, data=None):
+        """The tables of a GibbsPlan (its beam, bins and noise weights)."""
+        kap = plan.Npix / (4.0 * math.pi * plan.noise_var[:plan.F])
+        return cls(plan.F, plan.L, plan.nchains if nchains is None else nchains, plan.bl, plan.bins, kap,
+                   maxbins=plan.maxbins, device=plan.device, data=data)
+
+    def reset(self):
+        C.check(self.lib.gs_wf_reset(C.ptr(self.data), self.F, self.nchains, self.L, C.stream_ptr()), "gs_wf_reset")
+        self._count = 0
+
+    def _check_d(self, d_alm):
+        if d_alm.dtype != torch.float64 or not d_alm.is_cuda or d_alm.numel() != self.F * self.NR:
+            raise ValueError(f"wiener posterior: d_alm must be a float64 device tensor [{self.F}, (L+1)^2]")
+
+    def data_moments(self, d_alm):
+        """S_l = sum_m d_lm d_lm^T [nspec, L+1] of the data tensor (gs_wf_moments),
+        kept for update() and power(): once per data tensor."""
+        self._check_d(d_alm)
+        mom = torch.zeros(self.nspec, self.L + 1, dtype=torch.float64, device=self.data.device)
+        C.check(self.lib.gs_wf_moments(self.L, self.F, C.ptr(d_alm), C.ptr(mom), C.stream_ptr()), "gs_wf_moments")
+        self.moments = mom
+        return mom
+
+    def update(self, trace, capacity, first_iteration, nsteps, count_after=None):
+        """Add iterations first_iteration .. first_iteration + nsteps - 1 from the
+        trace ring [capacity, nchains, nspec, maxbins] (iteration it in slot
+        (it - 1) % capacity).  count_after: the samples per chain after this
+        call (default: nsteps more than after the last one)."""
+        if self.moments is None:
+            raise RuntimeError("wiener posterior: data_moments(d_alm) first")
+        if trace.dtype != torch.float64 or not trace.is_cuda:
+            raise ValueError("wiener posterior: the trace must be a float64 device tensor")
+        if trace.numel() < int(capacity) * self.nchains * self.nspec * self.maxbins:
+            raise ValueError("wiener posterior update: the trace is smaller than capacity rows")
+        k = self._count + int(nsteps) if count_after is None else int(count_after)
+        C.check(self.lib.gs_wf_update(C.ptr(self.data), self.F, self.nchains, self.L, self.maxbins, C.ptr(self.bl),
+                                      C.ptr(self.ell2bin), *self.kappa, C.ptr(self.moments), C.ptr(trace),
+                                      int(capacity), int(first_iteration), int(nsteps), k, C.stream_ptr()),
+                "gs_wf_update")
+        if int(nsteps) > 0:
+            self._count = k
+
+    @property
+    def n(self):
+        """Samples per chain (reads the device count: synchronises)."""
+        return int(self.data[:1].view(torch.int64).item())
+
+    def fields(self):
+        """The per-(chain, l) planes as a view [NFLD, nchains, L+1]."""
+        return self.data[self.HDR:].view(self.nfld, self.nchains, self.L + 1)
+
+    def _gathered(self, gather):
+        if gather is None:
+            return self.data, self.nchains
+        body = gather(self.fields().contiguous(), dim=1)
+        return torch.cat([self.data[:self.HDR], body.reshape(-1)]), int(body.shape[1])
+
+    def finish(self, d_alm, gather=None):
+        """Device tensors: alm_mean, alm_var, alm_rhat [F, (L+1)^2], chain_alm_mean
+        [C, F, (L+1)^2] and n (samples per chain).  gather (ShardContext.gather):
+        the planes are all-gathered along the chain axis first and the finish
+        runs over every rank's chains."""
+        self._check_d(d_alm)
+        data, nch = self._gathered(gather)
+        z = lambda *shape: torch.zeros(*shape, self.F, self.NR, dtype=torch.float64, device=self.data.device)
+        mean, var, cm, rhat = z(), z(), z(nch), z()
+        C.check(self.lib.gs_wf_finish(C.ptr(data), self.F, nch, self.L, C.ptr(d_alm), C.ptr(mean), C.ptr(var),
+                                      C.ptr(cm), C.ptr(rhat), C.stream_ptr()), "gs_wf_finish")
+        return dict(alm_mean=mean, alm_var=var, chain_alm_mean=cm, alm_rhat=rhat, n=self.n)
+
+    def power(self, gather=None):
+        """Device tensors power_of_mean, mean_power [nspec, L+1] (TE included for
+        F = 3) and op_mean [nop, L+1], the posterior-averaged operator."""
+        if self.moments is None:
+            raise RuntimeError("wiener posterior: data_moments(d_alm) first")
+        data, nch = self._gathered(gather)
+        z = lambda n: torch.zeros(n, self.L + 1, dtype=torch.float64, device=self.data.device)
+        pom, mp, op = z(self.nspec), z(self.nspec), z(self.nop)
+        C.check(self.lib.gs_wf_power(C.ptr(data), self.F, nch, self.L, C.ptr(self.moments), C.ptr(pom), C.ptr(mp),
+                                     C.ptr(op), C.stream_ptr()), "gs_wf_power")
+        return dict(power_of_mean=pom, mean_power=mp, op_mean=op)
+
+
 def br_shapes(nfields, bins, maxbins=None):
     """The shape table of the centered conditionals (gs_br.hip): (alpha [nspec,
     maxbins], half_mask).  With n_b = l1^2 - l0^2: alpha = n_b / 2 - 1 for the

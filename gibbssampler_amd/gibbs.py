@@ -58,6 +58,11 @@ and its ``loglike(theory)`` scores theory spectra named after the run).
 Masked polarization runs only: ``skymap_summary`` (True or {start, pixels,
 every}: the streaming posterior mean, variance and R-hat of the sky map the CR
 step produces, kept on the device; the ``posterior_skymap`` property).
+Full-sky harmonic runs of all three samplers: ``wiener_posterior`` (True or
+{start}: the Rao-Blackwellised posterior sky map -- mean, variance, R-hat, the
+per-l powers with TE and the posterior-averaged Wiener-filter operator -- from
+the D_l chain alone through the closed-form centered operator; the
+``posterior_wiener`` property; it too allows ``keep_history=False``).
 """
 import os
 import time
@@ -166,8 +171,13 @@ class GibbsSampler:
                  chain0=0, reference_quirks=True, noise_pol=None, proposal_variances=None,
                  metropolis_blocks=None, n_iter_metropolis=1, mask_path=None, distributed=False,
                  dist_backend=None, keep_skymap=False, sht_mode="auto", summary=None, keep_history=True,
-                 blackwell_rao=None, keep_scales=False, br_likelihood=None, br_samples=None, skymap_summary=None):
+                 blackwell_rao=None, keep_scales=False, br_likelihood=None, br_samples=None, skymap_summary=None,
+                 wiener_posterior=None):
         self.shard = None
+        # Rao-Blackwellised posterior sky map of full-sky runs (BatchedRunner.run(wiener_posterior=))
+        from .samplers import check_wiener_posterior
+        check_wiener_posterior(wiener_posterior)
+        self.wiener_posterior = wiener_posterior if wiener_posterior else None
         # streaming posterior mean / variance of the sky map (masked drivers' run(skymap_summary=))
         from .samplers import check_skymap_summary
         check_skymap_summary(skymap_summary)
@@ -175,7 +185,8 @@ class GibbsSampler:
         self._masked_runner = None
         # streaming posterior summary (samplers.BatchedRunner.run(summary=, keep_history=))
         from .samplers import check_summary
-        check_summary(summary, keep_history or bool(blackwell_rao) or bool(br_likelihood) or bool(br_samples))
+        check_summary(summary, keep_history or bool(blackwell_rao) or bool(br_likelihood) or bool(br_samples) or
+                      bool(wiener_posterior))
         self.summary = summary if summary else None
         self.keep_history = bool(keep_history)
         # streaming Blackwell-Rao posteriors and the scale history
@@ -361,8 +372,10 @@ class GibbsSampler:
         init = dls_init if isinstance(dls_init, dict) or resume is not None else {self.spectra[0]: dls_init}
         kw = {"n_warmup": self.n_warmup, "target_accept": self.target_accept} if self.n_warmup else {}
         if self.summary is not None or self.blackwell_rao is not None or self.br_likelihood is not None or \
-                self.br_samples is not None:
+                self.br_samples is not None or self.wiener_posterior is not None:
             kw.update(summary=self.summary, keep_history=self.keep_history)
+        if self.wiener_posterior is not None:
+            kw.update(wiener_posterior=self.wiener_posterior)
         if self.br_samples is not None:
             kw.update(br_samples=self.br_samples)
         if self.br_likelihood is not None:
@@ -462,6 +475,12 @@ class GibbsSampler:
                 raise NotImplementedError("br_samples: masked and TT-pixel runs do not go through the device "
                                           "C_l draw that records the scales; full-sky harmonic (all_sph) runs only")
 
+    def _check_wiener(self):
+        if self.wiener_posterior is not None and (self.mask is not None or getattr(self, "tt_pixel", False)):
+            raise NotImplementedError("wiener_posterior: masked and TT-pixel runs have no closed-form per-l CR "
+                                      "operator; the Rao-Blackwellised sky map covers the full-sky harmonic "
+                                      "(all_sph) samplers only (masked runs: skymap_summary is their route)")
+
     def _check_skymap(self):
         if self.skymap_summary is not None and (self.mask is None or getattr(self, "tt_pixel", False)):
             raise NotImplementedError("skymap_summary: full-sky harmonic (all_sph) and TT-pixel runs take their CR "
@@ -479,6 +498,26 @@ class GibbsSampler:
         if runner is None or getattr(runner, "_skymap", None) is None:
             raise RuntimeError("posterior_skymap: nothing has run yet with skymap_summary=")
         return runner.skymap_summary(self.shard.gather if self.shard is not None else None)
+
+    @property
+    def posterior_wiener(self):
+        """After a full-sky run with wiener_posterior=: numpy arrays with the names
+        and shapes of the masked runs' posterior_skymap -- alm_mean, alm_var,
+        alm_rhat [F, (L+1)^2], chain_alm_mean [chains, F, (L+1)^2], power_of_mean,
+        mean_power [nspec, L+1] (spectrum order, TE included for TEB), map_mean
+        [F, N_pix] (one alm2map of the mean: exact by linearity) -- plus op_mean
+        [nop, L+1], the posterior-averaged Wiener-filter operator, and n, the
+        samples per chain; over every rank's chains when distributed.  There is
+        no pixel variance: it needs the cross-l covariances of the operator."""
+        runner = self._runner
+        if runner is None or getattr(runner, "_wf", None) is None:
+            raise RuntimeError("posterior_wiener: nothing has run yet with wiener_posterior=")
+        out = runner.wiener_posterior(self.shard.gather if self.shard is not None else None)
+        from .sht import HealpixSHT
+        F = self.nfields
+        alm = torch.from_numpy(out["alm_mean"]).to(runner.plan.device)
+        out["map_mean"] = HealpixSHT(self.nside, self.lmax).alm2map_batch(alm[None], F)[0].cpu().numpy()
+        return out
 
     @property
     def posterior_summary(self):
@@ -578,6 +617,7 @@ class CenteredGibbs(GibbsSampler):
         self.tt_pixel = self._tt_pixel_path(all_sph)
         self._check_summary()
         self._check_skymap()
+        self._check_wiener()
         if self.tt_pixel:
             from .tt import TTCenteredConstrainedRealization, TTCenteredClsSampler
             m = self._tt_model(False)
@@ -638,6 +678,7 @@ class NonCenteredGibbs(GibbsSampler):
         self._set_warmup(n_warmup, target_accept)
         self._check_summary()
         self._check_skymap()
+        self._check_wiener()
         if self.tt_pixel:
             from .tt import TTNonCenteredConstrainedRealization, TTNonCenteredClsSampler
             m = self._tt_model(True)
@@ -692,6 +733,7 @@ class ASIS(GibbsSampler):
         self._set_warmup(n_warmup, target_accept)
         self._check_summary()
         self._check_skymap()
+        self._check_wiener()
         if self.tt_pixel:
             from .tt import TTCenteredConstrainedRealization, TTCenteredClsSampler, TTNonCenteredClsSampler
             m = self._tt_model(True)

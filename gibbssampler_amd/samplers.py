@@ -24,7 +24,8 @@ import numpy as np
 import torch
 
 from . import _capi as C
-from .engine import BlackwellRaoLikelihood, BlackwellRaoSamples, BlackwellRaoState, GibbsPlan, MH_ORDER, SummaryState
+from .engine import BlackwellRaoLikelihood, BlackwellRaoSamples, BlackwellRaoState, GibbsPlan, MH_ORDER, SummaryState, \
+    WienerPosterior
 
 INIT_ITER = 0xFFFFFFFF
 ADAPT_KAPPA = 0.6       # Robbins-Monro step n^-kappa of the warm-up adaptation
@@ -85,6 +86,22 @@ def check_skymap_summary(opt):
     if every < 1:
         raise ValueError("skymap_summary: every must be >= 1")
     return {"start": start, "pixels": bool(opts.get("pixels", False)), "every": every}
+
+
+def check_wiener_posterior(opt):
+    """run(wiener_posterior=...): None / False (off), True or {start: None};
+    returns None or {"start": int or None} (None: the iteration the warm-up
+    ends at, as the summary's)."""
+    if opt is None or opt is False:
+        return None
+    opts = {} if opt is True else dict(opt)
+    bad = set(opts) - {"start"}
+    if bad:
+        raise ValueError(f"wiener_posterior: unknown options {sorted(bad)}")
+    start = opts.get("start")
+    if start is not None and int(start) < 0:
+        raise ValueError("wiener_posterior: start must be >= 0")
+    return {"start": None if start is None else int(start)}
 
 
 def check_blackwell_rao(br, nfields, bins, dls_init=None, maxbins=None):
@@ -373,6 +390,10 @@ class BatchedRunner:
         # scales on the device and the iteration after which they are kept
         self._brs = None
         self.brs_start = 0
+        # Rao-Blackwellised posterior sky map (run(wiener_posterior=...)): the
+        # device state and the iteration after which it accumulates
+        self._wf = None
+        self.wf_start = 0
 
     def __del__(self):
         # dropped inside another sampler's capture: keep the kept hipGraphs, the
@@ -446,6 +467,8 @@ class BatchedRunner:
                       **{"brl_" + k: v for k, v in bl.tables().items()})
         if self._brs is not None:
             st.update(brs_start=int(self.brs_start), **{"brs_" + k: v for k, v in self._brs.state().items()})
+        if self._wf is not None:
+            st.update(wf_state=self._wf.data.cpu().clone(), wf_start=int(self.wf_start))
         if self.rng == "replay":
             name, keys, pos, has_gauss, cached = np.random.get_state()
             st.update(numpy_rng_keys=torch.from_numpy(np.asarray(keys, dtype=np.int64)), numpy_rng_pos=int(pos),
@@ -513,6 +536,12 @@ class BatchedRunner:
             self.brs_start = int(st["brs_start"])
         else:
             self._brs = None
+        # and one without the posterior sky map's
+        if st.get("wf_state") is not None:
+            self._wf_alloc(data=st["wf_state"])
+            self.wf_start = int(st["wf_start"])
+        else:
+            self._wf = None
         if self.rng == "replay" and "numpy_rng_keys" in st:
             np.random.set_state(("MT19937", st["numpy_rng_keys"].numpy().astype(np.uint32), st["numpy_rng_pos"],
                                  st["numpy_rng_has_gauss"], st["numpy_rng_cached"]))
@@ -689,6 +718,38 @@ class BatchedRunner:
             raise RuntimeError("br_samples: the last run() kept no sample bank (run(br_samples=...))")
         return self._brs
 
+    # -- Rao-Blackwellised posterior sky map -------------------------------------------------
+    def _wf_alloc(self, data=None):
+        """The posterior sky map's state (kept across runs and zeroed), or the
+        restored state `data`."""
+        if data is None and self._wf is not None:
+            self._wf.reset()
+            return
+        self._wf = WienerPosterior.from_plan(self.plan, data=data)
+        self._wf.data_moments(self.d)
+
+    def _wf_update(self, trace, capacity, it0, k):
+        """As _br_update, on the D_l trace ring and wf_start."""
+        first = max(it0, self.wf_start) + 1
+        n = it0 + k - first + 1
+        if n > 0:
+            self._wf.update(trace, capacity, first, n)
+
+    def wiener_posterior(self, gather=None):
+        """The Rao-Blackwellised posterior sky map of the last
+        run(wiener_posterior=...), numpy: alm_mean, alm_var, alm_rhat [F, (L+1)^2],
+        chain_alm_mean [C, F, (L+1)^2], power_of_mean, mean_power [nspec, L+1]
+        (TE included for TEB), op_mean [nop, L+1] (the posterior-averaged
+        Wiener-filter operator: M00, M01, M10, M11, M22 for TEB, M_f otherwise)
+        and n, the samples per chain.  gather as in summary()."""
+        if self._wf is None:
+            raise RuntimeError("wiener_posterior: the last run() kept no posterior sky map "
+                               "(run(wiener_posterior=True))")
+        gather = gather if gather is not None else self._gather
+        out = self._wf.finish(self.d, gather)
+        out.update(self._wf.power(gather))
+        return {k: (v.cpu().numpy() if torch.is_tensor(v) else v) for k, v in out.items()}
+
     def summary_accept_counts(self, gather=None):
         """(counts per spectrum {s: int64 [chains, flags]}, n) of the summarised
         iterations (None for the centered sampler)."""
@@ -798,7 +859,7 @@ class BatchedRunner:
     # -- a whole run --------------------------------------------------------------------
     def run(self, dls_init, n_iter, timings=False, gather=None, graph_chunk=32, resume=None, n_warmup=0,
             target_accept=0.25, summary=None, keep_history=True, blackwell_rao=None, keep_scales=False,
-            br_likelihood=None, br_samples=None):
+            br_likelihood=None, br_samples=None, wiener_posterior=None):
         """n_iter iterations from dls_init; returns (histories, accepts[, step
         times]).  gather: ShardContext.gather of a torchrun job -- the device
         histories of every rank are all-gathered along the chain axis (global
@@ -848,7 +909,14 @@ class BatchedRunner:
         columns, and bank.loglike(theory) scores theory spectra that need not be
         known before the run.  Centered and ASIS only; it lifts the need for a
         summary of keep_history=False, and a resumed state that carries a bank
-        continues it (a state_dict holds the whole bank on the host)."""
+        continues it (a state_dict holds the whole bank on the host).
+        wiener_posterior: None, True or {"start": ...} -- the Rao-Blackwellised
+        posterior sky map (runner.wiener_posterior()): the closed-form centered
+        operator M_l(D_l), Sigma_l(D_l) of every iteration after `start` (as
+        the summary's) is accumulated from the D_l trace ring after every chunk
+        replay / eager step, O(chains L) per iteration and 160 B per (chain, l)
+        for TEB.  Every sampler kind; it lifts the need for a summary of
+        keep_history=False, and a resumed state that carries one continues it."""
         p = self.plan
         n_warmup = check_warmup(self.kind, self.rng, n_warmup, target_accept)
         br_opts = check_blackwell_rao(blackwell_rao, p.F, p.bins, dls_init, p.maxbins)
@@ -863,8 +931,9 @@ class BatchedRunner:
         if brs_opts is not None and self.kind == "noncentered":
             raise NotImplementedError("br_samples: the non-centered sampler has no centered conditional draw "
                                       "(use the centered or the ASIS sampler)")
+        wf_opts = check_wiener_posterior(wiener_posterior)
         sm_opts = check_summary(summary, keep_history or br_opts is not None or brl_opts is not None or
-                                brs_opts is not None)
+                                brs_opts is not None or wf_opts is not None)
         if p.scale_trace is not None:
             p.cls_scale_trace(None)         # left attached by a run that raised
         self._gather = gather
@@ -909,7 +978,13 @@ class BatchedRunner:
                 self._brs = BlackwellRaoSamples(p.nchains, p.F, p.bins, brs_opts["mask"],
                                                 self.iteration + n_iter - max(self.iteration, self.brs_start),
                                                 device=p.device)
-        sm, br, brl, brs = self._summary, self._br, self._brl, self._brs
+        if resume is None or self._wf is None:
+            if wf_opts is None:
+                self._wf = None
+            else:
+                self._wf_alloc()
+                self.wf_start = self.n_warmup if wf_opts["start"] is None else wf_opts["start"]
+        sm, br, brl, brs, wf = self._summary, self._br, self._brl, self._brs, self._wf
         if brs is not None:
             if self.kind == "noncentered":
                 raise NotImplementedError("br_samples: the non-centered sampler has no centered conditional draw")
@@ -919,7 +994,7 @@ class BatchedRunner:
             raise NotImplementedError("blackwell_rao: the non-centered sampler has no centered conditional draw")
         if brl is not None and self.kind == "noncentered":
             raise NotImplementedError("br_likelihood: the non-centered sampler has no centered conditional draw")
-        if sm is None and br is None and brl is None and brs is None and not keep_history:
+        if sm is None and br is None and brl is None and brs is None and wf is None and not keep_history:
             raise ValueError("keep_history=False needs a summary")
         with_scales = br is not None or brl is not None or brs is not None or keep_scales
         self.h_scales = None
@@ -988,6 +1063,8 @@ class BatchedRunner:
                     # one launch on the run's stream: the chunk's rows of the ring
                     # and its accept flags (the captured graphs are not touched)
                     self._summary_update(trace, chunk, self.iteration - k, k, acc_tr, acc_tr.stride(0))
+                if wf is not None:
+                    self._wf_update(trace, chunk, self.iteration - k, k)
                 if br is not None:
                     self._br_update(sc_tr, chunk, self.iteration - k, k)
                 if brl is not None:
@@ -1053,6 +1130,8 @@ class BatchedRunner:
             if sm is not None:
                 # the chain's D_l as a one-row trace
                 self._summary_update(self.dl, 1, self.iteration - 1, 1, self.accept, 0)
+            if wf is not None:
+                self._wf_update(self.dl, 1, self.iteration - 1, 1)
             if keep_history:
                 H[i + (1 if with_start else 0)].copy_(self.dl)
                 if self.kind != "centered":

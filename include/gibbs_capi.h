@@ -396,6 +396,58 @@ int gs_smap_finish(const void* state, int C, long long n, double* mean, double* 
 int gs_smap_power(int lmax, int nfields, const double* mean, const double* var, double* power_of_mean,
                   double* mean_power, void* stream);
 
+/* ---- Rao-Blackwellised posterior sky map of the full-sky samplers (gs_wf.hip) ----
+ * On the full sky the centered CR draw is s = M_l d + L_l z per l, so the
+ * posterior of the map follows from the D_l chain alone: E[s_lm | d] = mean_i
+ * M_l^i d_lm, Var[s_lm | d] = mean_i Sigma_l^i + Var_i(M_l^i d_lm), E[sigma_l | d]
+ * = mean_i (Sigma_l^i + M_l^i S_l M_l^i^T / (2l+1)) with S_l = sum_m d_lm d_lm^T.
+ * Plan-independent: any trace ring [capacity][nchains][nspec][maxbins] (nspec =
+ * 1, 2, 4 for nfields = 1, 2, 3) is accumulated through the centered operator
+ * (GS_MODE_CENTERED whatever sampler drew the D_l) of the DEVICE tables bl [L+1]
+ * and ell2bin [nspec][L+1] (int32, -1: unbinned, read as D_l = 0) and the noise
+ * weights k0..k2 = N_pix / (4 pi noise_var_f).  The state is a caller-owned DEVICE
+ * buffer of gs_wf_bytes bytes (8-byte aligned): 8 header doubles (int64 samples
+ * per chain first), then planes [nfld][nchains][L+1], l fastest -- the Welford
+ * means of the operator entries (nfields 3: M00, M01, M10, M11, M22; else M_f),
+ * the co-moment sums of the pairs that enter a slot's variance, the means of
+ * Sigma (s00, s11, s01, s22; else s_f) and of the per-l power (TT, EE, BB, TE;
+ * else per field); nfld = 20 for nfields 3, 4 nfields otherwise (gs_wf.hip
+ * documents the layout and every formula).
+ * gs_wf_reset zeroes the state.
+ * gs_wf_moments: the data moments S_l [nspec][L+1] of a real-layout d_alm
+ * [nfields][(L+1)^2] in spectrum order (TE = sum d_T d_E), rows added in the
+ * order m = 0 .. l; once per data tensor.
+ * gs_wf_update adds the nsteps consecutive iterations first_iteration,
+ * first_iteration + 1, ... (iteration it lies in slot (it - 1) % capacity;
+ * nsteps <= capacity, first_iteration >= 1) in one launch, one thread per
+ * (chain, l), in iteration order; count_after is the samples per chain after
+ * this call (given by the host: nothing is read back, the call is capturable
+ * and allocates nothing).  No atomics: the state's bits depend neither on how
+ * the iterations were cut into launches, nor on the capacity or a wrap, nor on
+ * the launch geometry, nor on the other chains.  Successive updates of one
+ * state must be ordered on one stream.
+ * gs_wf_finish, one thread per (field, slot) of d_alm, merges the C chains in
+ * chain order (Chan's update; C need not be the updating context's chain count:
+ * planes all-gathered along the chain axis are merged over every rank's
+ * chains).  Outputs, DEVICE fp64: alm_mean, alm_var, alm_rhat [nfields][(L+1)^2],
+ * chain_alm_mean [C][nfields][(L+1)^2]; alm_var is NaN when C k < 2, alm_rhat
+ * (Gelman-Rubin as gs_summary_finish on the series (M^i d)_f) for C = 1, k < 2
+ * or W == 0.
+ * gs_wf_power, one thread per l: power_of_mean [nspec][L+1] = Mbar S Mbar^T /
+ * (2l+1), mean_power [nspec][L+1], the pooled mean of the streamed power, and
+ * op_mean [nop][L+1] (nop = 5 for nfields 3, else nfields), the pooled operator:
+ * the posterior-averaged Wiener-filter transfer function. */
+int gs_wf_bytes(int nfields, int nchains, int lmax, long long* bytes /* HOST */);
+int gs_wf_reset(void* state, int nfields, int nchains, int lmax, void* stream);
+int gs_wf_moments(int lmax, int nfields, const double* d_alm, double* moments, void* stream);
+int gs_wf_update(void* state, int nfields, int nchains, int lmax, int maxbins, const double* bl, const int* ell2bin,
+                 double k0, double k1, double k2, const double* moments, const double* trace, int capacity,
+                 uint32_t first_iteration, int nsteps, long long count_after, void* stream);
+int gs_wf_finish(const void* state, int nfields, int C, int lmax, const double* d_alm, double* alm_mean,
+                 double* alm_var, double* chain_alm_mean, double* alm_rhat, void* stream);
+int gs_wf_power(const void* state, int nfields, int C, int lmax, const double* moments, double* power_of_mean,
+                double* mean_power, double* op_mean, void* stream);
+
 /* ---- streaming Blackwell-Rao marginal posteriors of the D_l (gs_br.hip) -------
  * The centered C_l draw samples D_b | s from an inverse-Gamma(alpha_b, beta_b)
  * (PolarizedCenteredClsSampler.sample, CenteredGibbs.py:54-93); the Blackwell-Rao
