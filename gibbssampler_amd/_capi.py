@@ -169,6 +169,16 @@ _SIGS = [
     ("gs_brt_tables", ctypes.c_int, [_VP] + [ctypes.c_int] * 4 + [_VP] * 8),
     ("gs_brt_mref", ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),
     ("gs_brt_chain", ctypes.c_int, [_VP] * 3 + [ctypes.c_int] * 4 + [_VP] * 8),
+    ("gs_gbr_info", ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [c_int_p] * 3),
+    ("gs_gbr_append", ctypes.c_int, [_VP] + [ctypes.c_int] * 5 + [_VP, _VP, ctypes.c_int, ctypes.c_uint32, ctypes.c_int,
+                                                                   ctypes.c_int, _VP]),
+    ("gs_gbr_marginals", ctypes.c_int, [_VP, _VP] + [ctypes.c_int] * 5 + [_VP] * 5 + [ctypes.c_int] + [_VP] * 4),
+    ("gs_gbr_marginals_finish", ctypes.c_int, [_VP] * 3 + [ctypes.c_int] * 3 + [_VP] * 5),
+    ("gs_gbr_tables", ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int] + [_VP] * 6),
+    ("gs_gbr_moments_work_bytes", ctypes.c_int, [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_longlong)]),
+    ("gs_gbr_moments", ctypes.c_int, [_VP, _VP] + [ctypes.c_int] * 5 + [_VP] * 4 + [ctypes.c_int, _VP, ctypes.c_longlong,
+                                                                                    _VP, _VP, _VP]),
+    ("gs_gbr_eval", ctypes.c_int, [_VP] + [ctypes.c_int] * 4 + [_VP] * 5 + [ctypes.c_int] + [_VP] * 4),
     ("gs_sht_create", ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(_VP)]),
     ("gs_sht_destroy", ctypes.c_int, [_VP]),
     ("gs_sht_info", ctypes.c_int, [_VP, c_int_p, c_int_p, ctypes.POINTER(ctypes.c_longlong),

@@ -23,7 +23,7 @@ SOURCES = [os.path.join(HERE, "csrc", "gs_kernels.hip"), os.path.join(HERE, "csr
            os.path.join(HERE, "csrc", "gs_br.hip"), os.path.join(HERE, "csrc", "gs_brl.hip"),
            os.path.join(HERE, "csrc", "gs_brs.hip"), os.path.join(HERE, "csrc", "gs_brh.hip"),
            os.path.join(HERE, "csrc", "gs_brt.hip"), os.path.join(HERE, "csrc", "gs_smap.hip"),
-           os.path.join(HERE, "csrc", "gs_wf.hip")]
+           os.path.join(HERE, "csrc", "gs_wf.hip"), os.path.join(HERE, "csrc", "gs_gbr.hip")]
 HEADERS = [os.path.join(HERE, "csrc", h) for h in ("gs_rng.h", "gs_common.h", "gs_bm_tables.h", "gs_block.h",
                                                          "gs_launch.h", "gs_sweep_pack.h")] + \
     [os.path.join(ROOT, "include", "gibbs_capi.h")]

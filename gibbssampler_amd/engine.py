@@ -23,6 +23,9 @@ from scipy.stats import invgamma
 from . import _capi as C
 
 SPECTRA = {1: ("TT",), 2: ("EE", "BB"), 3: ("TT", "EE", "BB", "TE")}
+# defaults of the Gaussianised Blackwell-Rao likelihood (interpolation error): nodes per column, span
+GBR_POINTS = 128
+GBR_SPAN = (0.5, 8.0)
 FIELDS = {1: ("TT",), 2: ("EE", "BB"), 3: ("TT", "EE", "BB")}
 MH_ORDER = {1: ("TT",), 2: ("EE", "BB"), 3: ("EE", "BB", "TT", "TE")}
 
@@ -1167,11 +1170,12 @@ class BlackwellRaoSamples:
     and coef are those of br_likelihood_tables; they do not depend on a theory."""
     HDR = 8
 
-    def __init__(self, nchains, nfields, bins, mask, capacity, device=None):
+    def __init__(self, nchains, nfields, bins, mask, capacity, device=None, draws=False):
         _require_gpu()
         self.lib = C.load()
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
         self.nchains, self.nfields = int(nchains), int(nfields)
+        self.draws = bool(draws)
         spectra = SPECTRA[self.nfields]
         self.bins = {s: np.asarray(bins[s], dtype=np.int64).copy() for s in spectra}
         self.mask = np.array(mask, dtype=bool)
@@ -1194,13 +1198,13 @@ class BlackwellRaoSamples:
         self.slice_rows, self.model_tile = sl.value, tm.value
         self.capacity = 0
         self._n = 0
-        self.X = self.r = None
+        self.X = self.r = self.Dl = None
         self._brt = None            # the tables and workspaces of loglike_t / loglike_grad_t, built on first use
         self.reserve(max(int(capacity), 1))
 
     def nbytes(self, capacity):
         """Device bytes of a bank of `capacity` rows per chain."""
-        return 8 * self.nchains * int(capacity) * (self.Jp + 1)
+        return 8 * self.nchains * int(capacity) * ((2 if self.draws else 1) * self.Jp + 1)
 
     def reserve(self, capacity):
         """Grow the bank to `capacity` rows per chain (rows [0, n) are kept)."""
@@ -1213,12 +1217,17 @@ class BlackwellRaoSamples:
         free = torch.cuda.mem_get_info(self.device)[0]
         if need > free:
             raise RuntimeError(f"Blackwell-Rao sample bank: {need} bytes ({self.nchains} chains x {capacity} rows x "
-                               f"{self.Jp + 1} values) do not fit in the {free} bytes of free device memory")
+                               f"{need // (8 * self.nchains * capacity)} values) do not fit in the {free} bytes of free device memory")
         X = torch.zeros(self.nchains, capacity, self.Jp, dtype=torch.float64, device=self.device)
         r = torch.zeros(self.nchains, capacity, dtype=torch.float64, device=self.device)
         if self._n:
             X[:, :self._n].copy_(self.X[:, :self._n])
             r[:, :self._n].copy_(self.r[:, :self._n])
+        if self.draws:
+            Dl = torch.zeros(self.nchains, capacity, self.Jp, dtype=torch.float64, device=self.device)
+            if self._n:
+                Dl[:, :self._n].copy_(self.Dl[:, :self._n])
+            self.Dl = Dl
         self.X, self.r, self.capacity = X, r, capacity
 
     @property
@@ -1226,11 +1235,20 @@ class BlackwellRaoSamples:
         """Rows (kept samples per chain) in the bank."""
         return self._n
 
-    def append(self, scales, ring_capacity, first_iteration, nsteps):
+    def append(self, scales, ring_capacity, first_iteration, nsteps, trace=None):
         """Append iterations first_iteration .. first_iteration + nsteps - 1 of the
-        scale ring (iteration it in slot (it - 1) % ring_capacity) at rows n .."""
+        scale ring (iteration it in slot (it - 1) % ring_capacity) at rows n ..; a
+        bank with draws also packs the same rows of the D_l trace ring `trace` (the
+        scale ring's layout and slots) into Dl (gs_gbr_append)."""
         if scales.numel() < int(ring_capacity) * self.nchains * self.nspec * self.maxbins:
             raise ValueError("Blackwell-Rao sample bank append: the scale ring is smaller than ring_capacity rows")
+        if self.draws:
+            if trace is None or trace.numel() < int(ring_capacity) * self.nchains * self.nspec * self.maxbins:
+                raise ValueError("Blackwell-Rao sample bank append: a bank with draws needs the D_l trace ring of "
+                                 "ring_capacity rows")
+            C.check(self.lib.gs_gbr_append(C.ptr(self.Dl), self.nchains, self.capacity, self.Ju, self.nspec,
+                                           self.maxbins, C.ptr(self.cols), C.ptr(trace), int(ring_capacity),
+                                           int(first_iteration), int(nsteps), self._n, C.stream_ptr()), "gs_gbr_append")
         C.check(self.lib.gs_brs_append(C.ptr(self.X), C.ptr(self.r), self.nchains, self.capacity, self.Ju, self.nspec,
                                        self.maxbins, C.ptr(self.cols), C.ptr(self.kind), C.ptr(self.coef),
                                        C.ptr(scales), int(ring_capacity), int(first_iteration), int(nsteps), self._n,
@@ -1607,21 +1625,112 @@ class BlackwellRaoSamples:
         tensor.  Second derivatives are not provided: loglike_hess has them."""
         return _BankLoglike.apply(theory, self)
 
+    # -- Gaussianised Blackwell-Rao likelihood (gs_gbr.hip) ----------------------------
+    def gaussianize(self, points=None, span=GBR_SPAN, gather=None):
+        """The Gaussianised Blackwell-Rao likelihood (Rudjord et al. 2009) fitted to
+        the bank, an engine.GaussianizedBlackwellRao: each inverse-Gamma column (all
+        of them for EE/BB and TT; TT, EE and BB of a TEB run, whose TE has no
+        one-dimensional marginal and is marginalised over) is mapped through its own
+        Blackwell-Rao marginal to a standard normal x_j(D_j), and a Gaussian (mu, C)
+        is fitted to the transformed draws of the bank.  Needs a bank with draws
+        (br_samples={"draws": True}).  points: G nodes per column (default
+        GBR_POINTS), geometric in D, of which nodes 1 .. G - 2 cover [a min D, b max
+        D] of the column's kept draws, span = (a, b) with a < 1 < b; the end nodes
+        lie outside that interval (default GBR_SPAN: b = 8 keeps the heavy right
+        tail of the low-l marginals on the grid).  gather (ShardContext.gather): the extremes, the
+        per-chain marginal partials and the per-chain moment sums are all-gathered
+        along the chain axis, and every rank fits the same likelihood.  Raises
+        ValueError when the kept samples are not more than the columns or the
+        covariance is not positive definite."""
+        if not self.draws:
+            raise ValueError("Blackwell-Rao sample bank: gaussianize needs the D_l draws in the bank "
+                             "(run(br_samples={..., 'draws': True}))")
+        G = GBR_POINTS if points is None else int(points)
+        a, b = (float(v) for v in span)
+        if not 8 <= G <= 256:
+            raise ValueError("gaussianize: points must lie in [8, 256]")
+        if not (0.0 < a < 1.0 < b and math.isfinite(b)):
+            raise ValueError("gaussianize: span = (a, b) needs 0 < a < 1 < b")
+        n = self._n
+        if n < 1:
+            raise ValueError("gaussianize: the bank is empty; more kept samples than columns are needed")
+        col = gbr_columns(self.nfields, self.bins, self.mask)
+        Jg = len(col["gcol"])
+        dev, f64 = self.device, torch.float64
+        gcol = torch.from_numpy(col["gcol"]).to(dev)
+        alpha = torch.from_numpy(col["alpha"]).to(dev)
+        half = torch.from_numpy(col["half"]).to(dev)
+        # the extremes of the kept draws per column (rows whose r is NaN are skipped rows)
+        good = ~torch.isnan(self.r[:, :n])
+        gl = gcol.long()
+        d = self.Dl[:, :n][:, :, gl]
+        lo = torch.where(good[:, :, None], d, torch.full_like(d, float("inf"))).amin(dim=(0, 1))
+        hi = torch.where(good[:, :, None], d, torch.full_like(d, float("-inf"))).amax(dim=(0, 1))
+        del d
+        if gather is not None:
+            lo, hi = gather(lo[None], dim=0).amin(dim=0), gather(hi[None], dim=0).amax(dim=0)
+        glo, gh = gbr_grid(lo.cpu().numpy(), hi.cpu().numpy(), G, a, b)
+        glo_d, gh_d = torch.from_numpy(glo).to(dev), torch.from_numpy(gh).to(dev)
+        st = C.stream_ptr()
+        lib = self.lib
+        m = torch.zeros(self.nchains, Jg, G, dtype=f64, device=dev)
+        S = torch.zeros(self.nchains, Jg, G, dtype=f64, device=dev)
+        cnt = torch.zeros(self.nchains, dtype=torch.int64, device=dev)
+        C.check(lib.gs_gbr_marginals(C.ptr(self.X), C.ptr(self.r), self.nchains, self.capacity, n, self.Ju, Jg,
+                                     C.ptr(gcol), C.ptr(alpha), C.ptr(half), C.ptr(glo_d), C.ptr(gh_d), G, C.ptr(m),
+                                     C.ptr(S), C.ptr(cnt), st), "gs_gbr_marginals")
+        part = {"m": m, "S": S, "cnt": cnt}
+        if gather is not None:
+            m, S, cnt = (gather(v, dim=0).contiguous() for v in (m, S, cnt))
+        logp = torch.zeros(Jg, G, dtype=f64, device=dev)
+        C.check(lib.gs_gbr_marginals_finish(C.ptr(m), C.ptr(S), C.ptr(cnt), int(m.shape[0]), Jg, G, C.ptr(alpha),
+                                            C.ptr(glo_d), C.ptr(gh_d), C.ptr(logp), st), "gs_gbr_marginals_finish")
+        tx = torch.zeros(Jg, G, 2, dtype=f64, device=dev)
+        tp = torch.zeros(Jg, G, 2, dtype=f64, device=dev)
+        mass = torch.zeros(Jg, dtype=f64, device=dev)
+        C.check(lib.gs_gbr_tables(C.ptr(logp), Jg, G, C.ptr(glo_d), C.ptr(gh_d), C.ptr(tx), C.ptr(tp), C.ptr(mass), st),
+                "gs_gbr_tables")
+        wb = ctypes.c_longlong()
+        C.check(lib.gs_gbr_moments_work_bytes(self.nchains, n, Jg, ctypes.byref(wb)), "gs_gbr_moments_work_bytes")
+        work = torch.empty(wb.value // 8, dtype=f64, device=dev)
+        S1 = torch.zeros(self.nchains, Jg, dtype=f64, device=dev)
+        S2 = torch.zeros(self.nchains, Jg, Jg, dtype=f64, device=dev)
+        C.check(lib.gs_gbr_moments(C.ptr(self.Dl), C.ptr(self.r), self.nchains, self.capacity, n, self.Ju, Jg,
+                                   C.ptr(gcol), C.ptr(tx), C.ptr(glo_d), C.ptr(gh_d), G, C.ptr(work), wb.value,
+                                   C.ptr(S1), C.ptr(S2), st), "gs_gbr_moments")
+        part.update(S1=S1, S2=S2)
+        if gather is not None:
+            S1, S2 = gather(S1, dim=0).contiguous(), gather(S2, dim=0).contiguous()
+        fit = gbr_finish(cnt.cpu().numpy(), S1.cpu().numpy(), S2.cpu().numpy())
+        out = GaussianizedBlackwellRao(self.nfields, self.bins, self.mask, col["tcol"], glo, gh, tx, tp, fit["mu"],
+                                       fit["chol"], fit["logdet"], fit["n"], mass, device=dev)
+        out.cov, out.chain_sums, out.logp = fit["cov"], part, logp
+        return out
+
     # -- checkpoints and files -------------------------------------------------------
     def state(self):
         """Host tensors of rows [0, n) and the mask (what a state_dict carries)."""
-        return {"X": self.X[:, :self._n].cpu().clone(), "r": self.r[:, :self._n].cpu().clone(),
-                "mask": torch.from_numpy(self.mask.copy())}
+        st = {"X": self.X[:, :self._n].cpu().clone(), "r": self.r[:, :self._n].cpu().clone(),
+              "mask": torch.from_numpy(self.mask.copy())}
+        if self.draws:
+            st["Dl"] = self.Dl[:, :self._n].cpu().clone()
+        return st
 
     @classmethod
     def from_state(cls, st, nfields, bins, capacity=None, device=None):
         """A bank holding the rows of state() (capacity: rows to make room for)."""
         X, r = torch.as_tensor(st["X"], dtype=torch.float64), torch.as_tensor(st["r"], dtype=torch.float64)
         n = int(r.shape[1])
+        Dl = st.get("Dl") if hasattr(st, "get") else None
         self = cls(int(r.shape[0]), nfields, bins, np.asarray(st["mask"], dtype=bool), max(n, int(capacity or 0)),
-                   device=device)
+                   device=device, draws=Dl is not None)
         if X.dim() != 3 or tuple(X.shape) != (self.nchains, n, self.Jp):
             raise ValueError("Blackwell-Rao sample bank state: X must be [nchains, n, Jp] of the mask's used columns")
+        if Dl is not None:
+            Dl = torch.as_tensor(Dl, dtype=torch.float64)
+            if tuple(Dl.shape) != tuple(X.shape):
+                raise ValueError("Blackwell-Rao sample bank state: Dl must have the shape of X")
+            self.Dl[:, :n].copy_(Dl)
         self.X[:, :n].copy_(X)
         self.r[:, :n].copy_(r)
         self._n = n
@@ -1631,9 +1740,10 @@ class BlackwellRaoSamples:
         """Write rows [0, n), the tables, the bins, the mask and nfields to an
         .npz file (numeric arrays only: loads with allow_pickle=False)."""
         st = self.state()
+        extra = {"Dl": st["Dl"].numpy()} if self.draws else {}
         np.savez(path, X=st["X"].numpy(), r=st["r"].numpy(), mask=self.mask, nfields=np.int64(self.nfields),
                  cols=self.cols.cpu().numpy(), kind=self.kind.cpu().numpy(), coef=self.coef.cpu().numpy(),
-                 **{"bins_" + s: b for s, b in self.bins.items()})
+                 **{"bins_" + s: b for s, b in self.bins.items()}, **extra)
 
     @classmethod
     def load(cls, path, device=None):
@@ -1641,10 +1751,171 @@ class BlackwellRaoSamples:
         with np.load(path, allow_pickle=False) as f:
             F = int(f["nfields"])
             bins = {s: f["bins_" + s] for s in SPECTRA[F]}
-            self = cls.from_state({"X": f["X"], "r": f["r"], "mask": f["mask"]}, F, bins, device=device)
+            st = {"X": f["X"], "r": f["r"], "mask": f["mask"]}
+            if "Dl" in f.files:
+                st["Dl"] = f["Dl"]
+            self = cls.from_state(st, F, bins, device=device)
             if not np.array_equal(f["cols"], self.cols.cpu().numpy()):
                 raise ValueError("Blackwell-Rao sample bank file: its columns do not match its bins and mask")
         return self
+
+
+
+
+def gbr_columns(nfields, bins, mask):
+    """The columns the Gaussianised Blackwell-Rao likelihood uses of a bank with
+    the used bins `mask`, numpy: gcol [Jg] int32 (positions among the bank's Ju
+    used columns), tcol [Jg] int32 (their entries of a theory [nspec * maxbins]),
+    alpha [Jg] and half [Jg] (beta = half x recorded scale) as br_shapes gives
+    them -- every inverse-Gamma column; of a TEB block TT and EE through their
+    inverse-Gamma marginals (alpha = n_b / 2 - 2, beta = Psi_ii / 2), TE left out."""
+    F = int(nfields)
+    mask = np.asarray(mask, dtype=bool)
+    maxbins = mask.shape[1]
+    _, _, cols, _ = _br_used("gbr_columns", F, np.ones((1,) + mask.shape), mask, bins)
+    alpha, half_mask = br_shapes(F, bins, maxbins)
+    a = alpha.reshape(-1)[cols]
+    keep = np.flatnonzero(np.isfinite(a))
+    if len(keep) == 0:
+        raise ValueError("gbr_columns: no inverse-Gamma column is used")
+    tcol = cols[keep]
+    half = np.where((half_mask >> (tcol // maxbins)) & 1, 0.5, 1.0)
+    return {"gcol": keep.astype(np.int32), "tcol": tcol.astype(np.int32), "alpha": np.ascontiguousarray(a[keep]),
+            "half": half.astype(np.float64)}
+
+
+def gbr_grid(dmin, dmax, G, a, b):
+    """(glo, gh [Jg]) of the node rule lD_g = glo + g gh: node 1 at log(a dmin), node
+    G - 2 at log(b dmax), so that every D in [a dmin, b dmax] has 1 <= u <= G - 2."""
+    dmin, dmax = np.asarray(dmin, dtype=np.float64), np.asarray(dmax, dtype=np.float64)
+    if not (np.all(np.isfinite(dmin)) and np.all(np.isfinite(dmax)) and np.all(dmin > 0)):
+        raise ValueError("gaussianize: the kept draws of a column are not positive and finite (or there are none)")
+    l1, l2 = np.log(a * dmin), np.log(b * dmax)
+    gh = (l2 - l1) / (G - 3)
+    return np.ascontiguousarray(l1 - gh), np.ascontiguousarray(gh)
+
+
+def gbr_finish(cnt, S1, S2):
+    """The Gaussian fit from the per-chain sums, numpy fp64 on the host, the chains
+    in chain order: N = sum cnt, mu = S1 / N, cov = (S2 - N mu mu^T) / (N - 1), its
+    lower Cholesky factor and log determinant.  Raises ValueError when N <= Jg or
+    cov is not positive definite."""
+    cnt = np.asarray(cnt, dtype=np.int64)
+    S1, S2 = np.asarray(S1, dtype=np.float64), np.asarray(S2, dtype=np.float64)
+    Jg = S1.shape[1]
+    N = int(cnt.sum())
+    if N <= Jg:
+        raise ValueError(f"Gaussianised Blackwell-Rao: {N} kept samples for {Jg} columns: more kept samples than "
+                         "columns are needed")
+    s1, s2 = np.zeros(Jg), np.zeros((Jg, Jg))
+    for c in range(S1.shape[0]):
+        s1 = s1 + S1[c]
+        s2 = s2 + S2[c]
+    mu = s1 / N
+    cov = (s2 - N * np.outer(mu, mu)) / (N - 1)
+    try:
+        if not np.all(np.isfinite(cov)):
+            raise np.linalg.LinAlgError("not finite")
+        chol = np.linalg.cholesky(cov)
+    except np.linalg.LinAlgError:
+        raise ValueError(f"Gaussianised Blackwell-Rao: the covariance of the {Jg} transformed columns over {N} kept "
+                         "samples is not positive definite: more kept samples than columns are needed") from None
+    return {"n": N, "mu": mu, "cov": cov, "chol": chol, "logdet": 2.0 * float(np.sum(np.log(np.diag(chol))))}
+
+
+class GaussianizedBlackwellRao:
+    """The Gaussianised Blackwell-Rao likelihood of BlackwellRaoSamples.gaussianize
+    (gs_gbr.hip documents the tables): per column the tables x(D) and log p(D) on a
+    grid uniform in log D, the mean mu and the lower Cholesky factor of the
+    covariance of the transformed draws (on the device), and
+      log L(D) = sum_j log p_j(D_j) - (x - mu)^T C^-1 (x - mu) / 2 + x^T x / 2 - log det C / 2.
+    For a TEB run this is the likelihood of (TT, EE, BB) with TE marginalised: the
+    theory's TE values are ignored.  It evaluates without the bank."""
+
+    def __init__(self, nfields, bins, mask, tcol, glo, gh, tx, tp, mu, chol, logdet, n, mass, device=None):
+        _require_gpu()
+        self.lib = C.load()
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+        self.nfields = int(nfields)
+        spectra = SPECTRA[self.nfields]
+        self.bins = {s: np.asarray(bins[s], dtype=np.int64).copy() for s in spectra}
+        self.mask = np.array(mask, dtype=bool)
+        self.nspec, self.maxbins = self.mask.shape
+        dev, f64 = self.device, torch.float64
+        tcol = np.asarray(tcol, dtype=np.int32)
+        self.Jg = int(len(tcol))
+        if self.Jg < 1 or tcol.min() < 0 or tcol.max() >= self.nspec * self.maxbins:
+            raise ValueError("Gaussianised Blackwell-Rao: tcol must lie in [0, nspec * maxbins)")
+        self.tcol = torch.from_numpy(tcol).to(dev).contiguous()
+        self.glo, self.gh, self.tx, self.tp, self.mu, self.chol, self._mass = (
+            torch.as_tensor(v, dtype=f64).to(dev).contiguous() for v in (glo, gh, tx, tp, mu, chol, mass))
+        self.G = int(self.tx.shape[1])
+        if tuple(self.tx.shape) != (self.Jg, self.G, 2) or tuple(self.tp.shape) != (self.Jg, self.G, 2) or \
+                tuple(self.chol.shape) != (self.Jg, self.Jg) or tuple(self.mu.shape) != (self.Jg,) or \
+                tuple(self.glo.shape) != (self.Jg,) or tuple(self.gh.shape) != (self.Jg,):
+            raise ValueError("Gaussianised Blackwell-Rao: tables must be tx, tp [Jg, G, 2], glo, gh, mu [Jg] and chol "
+                             "[Jg, Jg]")
+        self.logdet, self.n = float(logdet), int(n)
+        self.mass = self._mass.cpu().numpy()
+
+    def loglike_t(self, theory):
+        """Device tensors loglike [K], marginal [K] (sum_j log p_j) and outside [K]
+        (columns whose D lies off the usable interval; loglike is -inf there), n
+        and mass [Jg], of theory [K, nspec, maxbins] on this object's device: no
+        host round trip.  x and log p come from gs_gbr_eval; the triangular solve
+        and the norms go through torch."""
+        if not torch.is_tensor(theory) or theory.dim() != 3 or tuple(theory.shape[1:]) != (self.nspec, self.maxbins) \
+                or theory.shape[0] < 1 or theory.device != self.device:
+            raise ValueError("Gaussianised Blackwell-Rao: theory must be a tensor [K, nspec, maxbins] = "
+                             f"[K, {self.nspec}, {self.maxbins}] on the likelihood's device")
+        th = theory.detach().to(torch.float64).contiguous()
+        K = int(th.shape[0])
+        dev, f64 = self.device, torch.float64
+        x = torch.empty(K, self.Jg, dtype=f64, device=dev)
+        lp = torch.empty(K, self.Jg, dtype=f64, device=dev)
+        out = torch.empty(K, self.Jg, dtype=torch.int32, device=dev)
+        C.check(self.lib.gs_gbr_eval(C.ptr(th), K, self.nspec, self.maxbins, self.Jg, C.ptr(self.tcol), C.ptr(self.tx),
+                                     C.ptr(self.tp), C.ptr(self.glo), C.ptr(self.gh), self.G, C.ptr(x), C.ptr(lp),
+                                     C.ptr(out), C.stream_ptr()), "gs_gbr_eval")
+        outside = out.sum(dim=1)
+        marginal = lp.sum(dim=1)
+        z = torch.linalg.solve_triangular(self.chol, (x - self.mu).T.contiguous(), upper=False).T.contiguous()
+        corr = 0.5 * ((x * x).sum(dim=1) - (z * z).sum(dim=1)) - 0.5 * self.logdet
+        ll = torch.where(outside > 0, torch.full_like(marginal, float("-inf")), marginal + corr)
+        return {"loglike": ll, "marginal": marginal, "outside": outside, "n": self.n, "mass": self._mass}
+
+    def loglike(self, theory):
+        """loglike_t of K theory spectra given as BlackwellRaoSamples.loglike takes
+        them, numpy: {loglike [K], marginal [K], outside [K], n, mass [Jg]}.  For a TEB
+        run a dict theory may leave TE out; TE values that are given are not read."""
+        from .samplers import _br_theory_array, _br_theory_values
+        name = "Gaussianised Blackwell-Rao"
+        if self.nfields == 3 and isinstance(theory, dict) and "TE" not in theory:
+            theory = dict(theory, TE=np.zeros_like(np.atleast_2d(np.asarray(theory["TT"], dtype=np.float64))))
+        th = _br_theory_array(name, theory, SPECTRA[self.nfields], self.bins, self.nspec, self.maxbins)
+        if self.nfields == 3:
+            th[:, 3] = 0.0                  # TE is marginalised: its theory values are ignored
+        _br_theory_values(name, th, self.mask, self.nfields)
+        out = self.loglike_t(torch.from_numpy(np.ascontiguousarray(th)).to(self.device))
+        return {"loglike": out["loglike"].cpu().numpy(), "marginal": out["marginal"].cpu().numpy(),
+                "outside": out["outside"].cpu().numpy(), "n": self.n, "mass": self.mass.copy()}
+
+    def save(self, path):
+        """Write the tables, mu and the factor to an .npz file (numeric arrays only)."""
+        np.savez(path, nfields=np.int64(self.nfields), mask=self.mask, tcol=self.tcol.cpu().numpy(),
+                 glo=self.glo.cpu().numpy(), gh=self.gh.cpu().numpy(), tx=self.tx.cpu().numpy(),
+                 tp=self.tp.cpu().numpy(), mu=self.mu.cpu().numpy(), chol=self.chol.cpu().numpy(),
+                 logdet=np.float64(self.logdet), n=np.int64(self.n), mass=self.mass,
+                 **{"bins_" + s: b for s, b in self.bins.items()})
+
+    @classmethod
+    def load(cls, path, device=None):
+        """The likelihood of a save()d file."""
+        with np.load(path, allow_pickle=False) as f:
+            F = int(f["nfields"])
+            bins = {s: f["bins_" + s] for s in SPECTRA[F]}
+            return cls(F, bins, f["mask"], f["tcol"], f["glo"], f["gh"], f["tx"], f["tp"], f["mu"], f["chol"],
+                       float(f["logdet"]), int(f["n"]), f["mass"], device=device)
 
 
 class _BankLoglike(torch.autograd.Function):

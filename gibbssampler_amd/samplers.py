@@ -263,8 +263,9 @@ def check_br_likelihood(opts, nfields, bins, maxbins=None):
 def check_br_samples(opts, nfields, bins, maxbins=None):
     """run(br_samples=...): None / False (off), True or {"lrange": (lmin, lmax) or
     "mask": bool [nspec, maxbins] or {spectrum: [nbins]} (default: every drawn
-    bin), "start": as the summary's} -- the bins whose scales the sample bank
-    keeps.  Returns None or {mask, start}."""
+    bin), "start": as the summary's, "draws": bool (default False: keep the D_l
+    draws beside the scales, what bank.gaussianize needs)} -- the bins whose
+    scales the sample bank keeps.  Returns None or {mask, start, draws}."""
     from .engine import SPECTRA, br_likelihood_mask
     if opts is None or opts is False:
         return None
@@ -272,9 +273,11 @@ def check_br_samples(opts, nfields, bins, maxbins=None):
         opts = {}
     if not isinstance(opts, dict):
         raise ValueError("br_samples: True or a dict {[lrange | mask][, start]} is needed")
-    bad = set(opts) - {"lrange", "mask", "start"}
+    bad = set(opts) - {"lrange", "mask", "start", "draws"}
     if bad:
         raise ValueError(f"br_samples: unknown options {sorted(bad)}")
+    if not isinstance(opts.get("draws", False), (bool, np.bool_)):
+        raise ValueError("br_samples: draws must be True or False")
     if "lrange" in opts and "mask" in opts:
         raise ValueError("br_samples: give either lrange or mask")
     start = opts.get("start")
@@ -283,7 +286,7 @@ def check_br_samples(opts, nfields, bins, maxbins=None):
     F = int(nfields)
     drawn = br_likelihood_mask(F, bins, maxbins)
     mask = _br_used_mask("br_samples", opts, F, SPECTRA[F], bins, drawn)
-    return {"mask": mask, "start": None if start is None else int(start)}
+    return {"mask": mask, "start": None if start is None else int(start), "draws": bool(opts.get("draws", False))}
 
 
 def br_theory(name, theory, nfields, bins, mask):
@@ -531,7 +534,8 @@ class BatchedRunner:
             self._brl = None
         # and one without the sample bank's keys
         if st.get("brs_X") is not None:
-            self._brs = BlackwellRaoSamples.from_state({k: st["brs_" + k] for k in ("X", "r", "mask")}, p.F, p.bins,
+            self._brs = BlackwellRaoSamples.from_state({k: st["brs_" + k] for k in ("X", "r", "mask", "Dl")
+                                                        if st.get("brs_" + k) is not None}, p.F, p.bins,
                                                        device=p.device)
             self.brs_start = int(st["brs_start"])
         else:
@@ -704,12 +708,13 @@ class BatchedRunner:
         return res
 
     # -- Blackwell-Rao sample bank ---------------------------------------------------------
-    def _brs_append(self, scales, capacity, it0, k):
-        """As _br_update, for the sample bank and brs_start."""
+    def _brs_append(self, scales, capacity, it0, k, trace=None):
+        """As _br_update, for the sample bank and brs_start; trace: the D_l trace ring
+        beside the scale ring (read only by a bank that keeps the draws)."""
         first = max(it0, self.brs_start) + 1
         n = it0 + k - first + 1
         if n > 0:
-            self._brs.append(scales, capacity, first, n)
+            self._brs.append(scales, capacity, first, n, trace if self._brs.draws else None)
 
     def br_samples(self):
         """The sample bank of the last run(br_samples=...) (engine.BlackwellRaoSamples:
@@ -977,7 +982,7 @@ class BatchedRunner:
                 self.brs_start = self.n_warmup if brs_opts["start"] is None else brs_opts["start"]
                 self._brs = BlackwellRaoSamples(p.nchains, p.F, p.bins, brs_opts["mask"],
                                                 self.iteration + n_iter - max(self.iteration, self.brs_start),
-                                                device=p.device)
+                                                device=p.device, draws=brs_opts["draws"])
         if resume is None or self._wf is None:
             if wf_opts is None:
                 self._wf = None
@@ -985,6 +990,9 @@ class BatchedRunner:
                 self._wf_alloc()
                 self.wf_start = self.n_warmup if wf_opts["start"] is None else wf_opts["start"]
         sm, br, brl, brs, wf = self._summary, self._br, self._brl, self._brs, self._wf
+        if brs is not None and brs_opts is not None and brs.draws != brs_opts["draws"]:
+            raise ValueError("br_samples: the resumed sample bank was kept with draws=%s; a run that continues it cannot "
+                             "change that" % brs.draws)
         if brs is not None:
             if self.kind == "noncentered":
                 raise NotImplementedError("br_samples: the non-centered sampler has no centered conditional draw")
@@ -1070,7 +1078,7 @@ class BatchedRunner:
                 if brl is not None:
                     self._brl_update(sc_tr, chunk, self.iteration - k, k)
                 if brs is not None:
-                    self._brs_append(sc_tr, chunk, self.iteration - k, k)
+                    self._brs_append(sc_tr, chunk, self.iteration - k, k, trace)
                 if keep_scales:
                     Hs[done:done + k].copy_(sc_tr[:k] if r0 == 0 else sc_tr[(torch.arange(k) + r0) % chunk])
                 h0, h1 = (0 if done == 0 else off + done), off + done + k
@@ -1124,7 +1132,7 @@ class BatchedRunner:
             if brl is not None:
                 self._brl_update(sc1, 1, self.iteration - 1, 1)
             if brs is not None:
-                self._brs_append(sc1, 1, self.iteration - 1, 1)
+                self._brs_append(sc1, 1, self.iteration - 1, 1, self.dl)
             if keep_scales:
                 Hs[i].copy_(sc1[0])
             if sm is not None:

@@ -625,6 +625,56 @@ int gs_brs_hess(const double* X, const double* r, int nchains, int cap, int n, i
                 void* stream);
 int gs_brs_hess_finish(const double* num2, const void* state, int C, int K, int Ju, double* cov, void* stream);
 
+/* ---- Gaussianised Blackwell-Rao likelihood (gs_gbr.hip) -------------------------
+ * Rudjord et al. 2009: each inverse-Gamma column of the bank is mapped through its
+ * own Blackwell-Rao marginal to a standard normal x_j(D_j) and a Gaussian is
+ * fitted to the transformed draws.  All buffers DEVICE, fp64 unless noted.
+ * gs_gbr_append packs the D_l trace ring (the layout and the slot rule of the
+ * scale ring of gs_brs_append) into Dl [nchains][cap][Jp] at the used columns cols
+ * [Ju], rows row0 ... row0 + nsteps - 1: row i of Dl belongs to row i of X and r.
+ * The fit's Jg columns: gcol [Jg] (int32, positions in [0, Ju)), alpha [Jg], half
+ * [Jg] (beta = half X: 0.5 for TT and EE of a TEB block, else 1), and a grid of G
+ * nodes, 8 <= G <= 256, uniform in log D: lD_g = glo_j + g gh_j.  Nodes 1 and G - 2
+ * bound the usable interval; nodes 0 and G - 1 lie outside it.
+ * gs_gbr_marginals: per chain the online log-sum-exp (m, S) [nchains][Jg][G] of
+ * log IG(D_g; alpha_j, beta_cij) over rows [0, n) in row order, and cnt [nchains]
+ * (int64), the rows whose r is not NaN; a chain's partial depends on its rows
+ * alone.  gs_gbr_marginals_finish merges C chains (possibly all-gathered) in
+ * chain order into logp [Jg][G].
+ * gs_gbr_tables: the cumulative trapezoid in log D from both sides, mass [Jg], and
+ * the tables tx [Jg][G][2] = (x, dx/du) and tp [Jg][G][2] = (logp, dlogp/du), u
+ * the node coordinate.
+ * gs_gbr_moments: per chain S1 [nchains][Jg] = sum_i x_i and S2 [nchains][Jg][Jg]
+ * = sum_i x_i x_i^T over the rows whose r is not NaN, x_ij the cubic Hermite of
+ * log Dl_ij through tx, evaluated into LDS and contracted on the fp64 matrix
+ * cores (upper-triangular tile pairs, rows ascending; S2 exactly symmetric).
+ * work: gs_gbr_moments_work_bytes(nchains, n, Jg) bytes, one [Jq][Jq] + [Jq] tile
+ * per chain and row block, the blocks added in block order from 0.0;
+ * gs_gbr_info: the row blocks (at most 32) and their rows, a function of (n, Jg)
+ * alone, and the column tile.  For given (n, Jg, tables) a chain's sums are
+ * bit-identical whatever the other chains are.
+ * gs_gbr_eval: x [K][Jg], logp [K][Jg] and outside [K][Jg] (int32: 1 where D is
+ * off the usable interval; x = logp = 0 there) of theory [K][nspec][maxbins] at
+ * the entries tcol [Jg] (int32), the Hermite code of the fit.
+ * gs_gbr.hip documents the layout and the order of every operation. */
+int gs_gbr_info(int n, int Jg, int* nblk /* HOST */, int* block_rows /* HOST */, int* column_tile /* HOST */);
+int gs_gbr_append(double* Dl, int nchains, int cap, int Ju, int nspec, int maxbins, const int* cols,
+                  const double* trace, int capacity, uint32_t first_iteration, int nsteps, int row0, void* stream);
+int gs_gbr_marginals(const double* X, const double* r, int nchains, int cap, int n, int Ju, int Jg, const int* gcol,
+                     const double* alpha, const double* half, const double* glo, const double* gh, int G, double* m,
+                     double* S, long long* cnt, void* stream);
+int gs_gbr_marginals_finish(const double* m, const double* S, const long long* cnt, int C, int Jg, int G,
+                            const double* alpha, const double* glo, const double* gh, double* logp, void* stream);
+int gs_gbr_tables(const double* logp, int Jg, int G, const double* glo, const double* gh, double* tx, double* tp,
+                  double* mass, void* stream);
+int gs_gbr_moments_work_bytes(int nchains, int n, int Jg, long long* bytes /* HOST */);
+int gs_gbr_moments(const double* Dl, const double* r, int nchains, int cap, int n, int Ju, int Jg, const int* gcol,
+                   const double* tx, const double* glo, const double* gh, int G, void* work, long long work_bytes,
+                   double* S1, double* S2, void* stream);
+int gs_gbr_eval(const double* theory, int K, int nspec, int maxbins, int Jg, const int* tcol, const double* tx,
+                const double* tp, const double* glo, const double* gh, int G, double* x, double* logp, int* outside,
+                void* stream);
+
 /* The bank's likelihood of theory spectra that live on the device (gs_brt.hip):
  * engine.br_likelihood_tables and engine.br_likelihood_grad as kernels, so that
  * theory -> loglike (-> gradient) runs without a host round trip.  D [K][nspec]
